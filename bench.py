@@ -2,6 +2,12 @@
 """DGN-layer forward+backward throughput on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c2_b128|c1|c3|c4|c5] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up for W steps, times K steps and prints the line (``ms_per_step``: wall time of the K timed steps / K;
+``value``: edges per second over them); ``--dump-outputs DIR`` also writes what the last timed step computed as DIR/<name>.npy.
+Everything else described below (roofline legs, per-kernel table, CPU baseline, the other configs' sub-results, the data-parallel
+legs) runs only with ``--full``.
 
 With --gpus N > 1 and no launcher environment (RANK unset) the script re-executes itself under
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`` -- one rank per GPU over
@@ -14,13 +20,13 @@ The default workload is BASELINE.json configs[1]: ZINC-12k (all 12 000 molecules
 DGN towers (5 towers, hidden 70, mean/max/min/dir1-av/dir1-dx, 3 PNA scalers).  For N > 1 every rank
 processes its own 12k-molecule batch (weak scaling: seed 41 + rank), or -- ``--scaling strong`` -- its edge-balanced
 shard of ONE global batch (``dist.shard_by_edges``; SURVEY 8(e): ogbg-molhiv batch 2048 split over the ranks).
-The default single-GPU run also appends short sub-results (``extra``) for the other BASELINE configs (c1, c3, c4, c5) and for the
+The single-GPU ``--full`` run also appends short sub-results (``extra``) for the other BASELINE configs (c1, c3, c4, c5) and for the
 headline layer and the shipped ZINC json layer AT THE REFERENCE'S OWN BATCH SIZE (c2_b128, zinc_json_b128: 128 molecules, the graph-block
 route of csrc/dgn_blk_layer.hip), the batch-sized legs both eager and as a captured HIP graph (``captured_ms_per_step``), and the C5 graph
 through a whole simple layer forward (c5_layer: row f1; its ``frac`` is of the fp32 MFMA peak on the posttrans product); ``--all-extras``
 adds every other leg.
 
-Besides the contract keys the line carries
+Besides the contract keys the ``--full`` line carries
   roofline      the dominant aggregation kernel's algorithmic bytes / its measured launch duration
                 (HIP events on the launching stream) against the 8 TB/s HBM peak
   cpu_baseline  the oracle (reference-structured CPU restatement) timed on the host cores on a bounded
@@ -269,6 +275,41 @@ def step_kernel_table(step, dev, steps=5):
         return [dict(error=f"{type(exc).__name__}: {exc}"[:160])]
 
 
+DUMP_BYTES = 48 << 20      # --dump-outputs: bytes of all arrays written together (row samples and their row indices included)
+DUMP_WHOLE = 1 << 20       # arrays up to this size are always written whole
+
+
+def snapshot_outputs(named):
+    """{name: host array} of the floating-point tensors in `named`, taken right after the timed steps (before any other measurement runs
+    the step again).  Within DUMP_BYTES in all: if everything fits, every array whole; otherwise the arrays up to DUMP_WHOLE whole and
+    each larger one as a row sample sharing what they leave -- rows drawn with seed 0 and sorted, so the same shape always gives the same
+    rows -- plus `<name>_rows`, the sampled row indices (float64)."""
+    import numpy as np
+    named = {k: v.detach() for k, v in named.items() if v is not None and v.is_floating_point()}
+    size = {k: v.numel() * v.element_size() for k, v in named.items()}
+    big = [k for k in named if size[k] > DUMP_WHOLE] if sum(size.values()) > DUMP_BYTES else []
+    share = (DUMP_BYTES - sum(s for k, s in size.items() if k not in big)) // max(1, len(big))
+    out = {}
+    for k, v in named.items():
+        if v.dtype not in (torch.float32, torch.float64):
+            v = v.float()
+        if k in big:
+            keep = min(v.shape[0], max(1, share // (v[0].numel() * v.element_size() + 8)))
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], keep, replace=False))
+            out[k + "_rows"] = rows.astype(np.float64)
+            v = v.index_select(0, torch.from_numpy(rows).to(v.device))
+        out[k] = v.cpu().numpy()
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array of snapshot_outputs()."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k.replace(os.sep, "_") + ".npy"), a)
+
+
 def build_batch(wl, seed, dev, shard=None):
     """``shard = (rank, world)``: keep this rank's edge-balanced share of the batch's graphs (strong scaling)."""
     kind, kw = wl["gen"]
@@ -359,6 +400,7 @@ def run_layer_workload(args, wl, rank, world, dev, steps=None, warmup=None, tag=
     """One layer workload: timed steps (contract timing) + the roofline of its aggregation kernels on rank 0."""
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
+    dump = args.dump_outputs and rank == 0 and tag is None      # (the headline run only, never a leg of --full)
     tag = tag or args.workload
     # weak scaling: every rank draws its OWN batch (generator seed 41 + rank; 41 = BASELINE config seed), so shapes differ
     # slightly between ranks as they do in a real data-parallel epoch; strong scaling: ONE global batch (seed 41 on every
@@ -387,6 +429,7 @@ def run_layer_workload(args, wl, rank, world, dev, steps=None, warmup=None, tag=
     reducer = ddist.FlatGradAllReduce(layer.parameters()) if torch.distributed.is_initialized() else None
 
     params = list(layer.parameters())      # (what an optimizer holds; walking the module tree costs 0.1 ms per step)
+    last = [None]                          # the output of the latest step (--dump-outputs)
 
     def step():
         graph._wcache.clear()              # per-edge weights are recomputed every step (eig flips per batch)
@@ -399,6 +442,8 @@ def run_layer_workload(args, wl, rank, world, dev, steps=None, warmup=None, tag=
         y.backward(ct)
         if reducer is not None:
             reducer()
+        if dump:
+            last[0] = y.detach()
 
     if args.hipgraph:
         # Launch-bound batches (the reference's batch of 128 molecules: ~80 launches around 0.4 ms of kernels): the whole
@@ -409,12 +454,16 @@ def run_layer_workload(args, wl, rank, world, dev, steps=None, warmup=None, tag=
         reducer = None      # (a forced single-rank process group: nothing to reduce)
         def bare_step():                   # (gradients stay None: the captured backward writes fresh ones per replay)
             graph._wcache.clear()
-            layer(graph, h, ef, snorm).backward(ct)
+            y = layer(graph, h, ef, snorm)
+            y.backward(ct)
+            if dump:
+                last[0] = y.detach()       # (detached: no autograd graph of an earlier step may be released inside the capture)
 
         def reset():
             h.grad = None
             for p in params:
                 p.grad = None
+            last[0] = None
 
         def warm_step():
             reset()
@@ -451,6 +500,13 @@ def run_layer_workload(args, wl, rank, world, dev, steps=None, warmup=None, tag=
 
     result = dict(ms_per_step=ms, value=total_edges / (ms * 1e-3), edges_per_rank=E, nodes_per_rank=N,
                   scaling="strong" if strong else "weak")
+    if dump:
+        named = {"out": last[0], "h.grad": h.grad, "edge_features.grad": None if ef_leaf is None else ef_leaf.grad}
+        named.update({n + ".grad": p.grad for n, p in layer.named_parameters()})
+        named.update(layer.named_buffers())
+        result["outputs"] = snapshot_outputs(named)
+    if not args.full:
+        return result, batch
     blk_rows = []
     if rank == 0:
         # the step against the layer's mandatory traffic (roofline.step), and where its time goes kernel by kernel (full record only)
@@ -628,6 +684,7 @@ def run_c5(args, wl, rank, world, dev, steps=None, warmup=None, tag=None):
     """Single forward pass of the fused aggregation on the power-law graph (HBM-roofline run)."""
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
+    dump = args.dump_outputs and rank == 0 and tag is None
     kw = dict(wl["gen"][1])
     if args.scale != 1.0:
         kw["num_nodes"] = int(kw["num_nodes"] * args.scale)
@@ -687,8 +744,9 @@ def run_c5(args, wl, rank, world, dev, steps=None, warmup=None, tag=None):
     e_total = torch.tensor([float(E)], dtype=torch.float64, device=dev)
     if torch.distributed.is_initialized():
         torch.distributed.all_reduce(e_total)
+    outputs = snapshot_outputs({"out": out}) if dump else None
     ranks_info = None
-    if torch.distributed.is_initialized():
+    if torch.distributed.is_initialized() and args.full:
         ms_ag = None
         if partition:
             # the exchange between two sharded layers: the F-wide output rows of every shard all-gathered (dist.all_gather_rows)
@@ -701,7 +759,9 @@ def run_c5(args, wl, rank, world, dev, steps=None, warmup=None, tag=None):
                   eig=eig_info or "random columns", scaling="strong" if partition else "weak",
                   parallelism=(f"1 graph, {world} destination-range shards (balanced edges), features replicated, no exchange "
                                f"inside the sweep") if partition else (f"{world} independent replicas" if world > 1 else "single GPU"))
-    if rank == 0:
+    if dump:
+        result["outputs"] = outputs
+    if rank == 0 and args.full:
         A, S, Ku, x, r = plan_model(plan)
         ms_f = event_ms(step, max(3, steps), dev)
         ms_w = event_ms(lambda: dgn_amd.compute_edge_weights(graph, plan.channels, eig=eig), 3, dev)
@@ -746,15 +806,28 @@ def run_c5_layer(args, wl, rank, world, dev, steps=None, warmup=None, tag=None):
     from dgn_amd.dgn_layer import node_linear
     w_f = lin.weight.detach().reshape(F_, S_, A_ * F_).permute(1, 0, 2).reshape(S_ * F_, A_ * F_).contiguous()
 
+    dump = args.dump_outputs and tag is None
+    last = [None]                          # the output of the latest step (--dump-outputs)
+
     def step():
         with torch.no_grad():
-            return layer(graph, h, None, None)
+            y = layer(graph, h, None, None)
+            if dump:
+                last[0] = y
+            return y
 
     parts = {}
     with torch.no_grad():
         for _ in range(warmup):
             step()
         ms = event_ms(step, steps, dev, warm=0)
+        outputs = snapshot_outputs({"out": last[0]}) if dump else None
+        last[0] = None
+        if not args.full:
+            result = dict(ms_per_step=ms, value=E / (ms * 1e-3), edges_per_rank=E, nodes_per_rank=N, scaling="weak", parallelism="single GPU")
+            if outputs is not None:
+                result["outputs"] = outputs
+            return result, None
         agg = layer.aggregate(graph, h, plan, graph.ndata["eig"])
         parts["sweep (scalers folded: [N, 1024] aggregates written)"] = event_ms(lambda: layer.aggregate(graph, h, plan, graph.ndata["eig"]), steps, dev)
         parts["posttrans product 1024 -> 384 (exact-fp32 MFMA)"] = event_ms(lambda: node_linear(agg, w_f), steps, dev)
@@ -787,6 +860,8 @@ def run_c5_layer(args, wl, rank, world, dev, steps=None, warmup=None, tag=None):
                                            unfused_layer_bytes=unfused_bytes, sweep_only_bytes_c5=algorithmic_bytes(N, E, F_, A, S, Ku, x, r)[0],
                                            hbm_frac_on_fused_bytes=fused_bytes / (ms * 1e-3) / HBM_PEAK,
                                            mfma_floor_ms=flops / MFMA_F32_PEAK * 1e3)))
+    if outputs is not None:
+        result["outputs"] = outputs
     return result, None
 
 
@@ -1373,10 +1448,10 @@ def main():
     ap.add_argument("--c5-eig-iters", type=int, default=40)
     ap.add_argument("--aggregators", default=None, help="override the workload's aggregator string (experiments)")
     ap.add_argument("--scalers", default=None, help="override the workload's scaler string (experiments)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sub-results of the other configs in the default run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the sub-results of the other configs")
     ap.add_argument("--all-extras", action="store_true",
-                    help="default run: also the non-BASELINE legs (c2c, c2e, json configs, mega batches, batch-128, inference, nets)")
+                    help="implies --full: also the non-BASELINE legs (c2c, c2e, json configs, mega batches, batch-128, inference, nets)")
     ap.add_argument("--hipgraph", action="store_true",
                     help="layer workloads, 1 GPU: capture the step (edge weights + forward + backward) in a HIP graph and replay it")
     ap.add_argument("--gemm-tuning", default="off", choices=["off", "file", "tune"],
@@ -1384,9 +1459,19 @@ def main():
                          "(default: every Linear of the benched layers runs on this library's own kernels), 'file' replays "
                          "dgn_amd/tunableop_gfx950.csv, 'tune' tunes and rewrites it")
     ap.add_argument("--cpu-sample-graphs", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline timing: roofline legs, per-kernel table, CPU baseline, regression check against "
+                         "the committed record, the other configs' sub-results (extra) and, with --gpus N > 1, the data-parallel legs.  "
+                         "Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (output, input and parameter gradients, "
+                         "updated running statistics) as DIR/<name>.npy; arrays over the size budget as a fixed, seeded row sample "
+                         "(DIR/<name>.npy + DIR/<name>_rows.npy)")
     args = ap.parse_args()
     if args.scaling is None:
         args.scaling = "weak"
+    if args.all_extras:
+        args.full = True          # (every leg of the full run: implies it)
 
     spawn_ranks_if_needed(args)
     if int(os.environ.get("WORLD_SIZE", 1)) != args.gpus:
@@ -1405,11 +1490,14 @@ def main():
     runner = run_c5 if wl["type_net"] == "op" else (run_c5_layer if wl["type_net"] == "layer_fwd" else run_layer_workload)
     res = runner(args, wl, rank, world, dev)
     if rank != 0:
-        run_dp_extras(args, rank, world, dev, None)
+        if args.full:
+            run_dp_extras(args, rank, world, dev, None)
         if torch.distributed.is_initialized():
             torch.distributed.destroy_process_group()
         return
     result, batch = res
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, result.pop("outputs"))
     backend = torch.distributed.get_backend() if torch.distributed.is_initialized() else None
     line = dict(metric={"op": "dgn_aggregation_fwd_edges_per_sec", "layer_fwd": "dgn_layer_fwd_edges_per_sec"}.get(wl["type_net"], "dgn_layer_fwd_bwd_edges_per_sec"),
                 value=result["value"], unit="edges/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
@@ -1434,10 +1522,14 @@ def main():
         line["ranks"] = result["ranks"]
         if result.get("allreduce"):
             line["allreduce"] = result["allreduce"]
+    line["cpu_baseline"] = None
+    if not args.full:
+        emit(line, args)
+        if torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()
+        return
     if world == 1 and not args.no_cpu_baseline and batch is not None:
         line["cpu_baseline"] = cpu_baseline(wl, batch, min(args.cpu_sample_graphs, len(batch["sizes"])))
-    else:
-        line["cpu_baseline"] = None
     if world == 1 and args.workload == "c2" and not args.hipgraph and not args.aggregators and not args.scalers:
         regression_warnings({}, headline=line)
     if world == 1 and args.workload == "c2" and not args.no_extras and not args.hipgraph and not args.aggregators and not args.scalers:

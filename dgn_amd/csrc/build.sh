@@ -24,7 +24,10 @@ for f in "$here"/*.hip; do
   u="$(basename "$f" .hip)"; seen="$(mktemp)"; deps_of "$f"
   { printf '%s/%s.o:' "$objdir" "$u"; tr '\n' ' ' < "$seen"; echo; } > "$objdir/$u.d"; rm -f "$seen"
 done
-make -s -j "${DGN_JOBS:-$(nproc)}" -f "$here/Makefile" OUT="$out" OBJDIR="$objdir" ${HIPCC:+HIPCC="$HIPCC"}
+# (at most 16 compile jobs unless DGN_JOBS says otherwise: nproc counts every core of a shared host, not the ones this build may use)
+jobs="${DGN_JOBS:-${MAX_JOBS:-$(nproc)}}"
+[ -n "${DGN_JOBS:-}" ] || [ "$jobs" -le 16 ] || jobs=16
+make -s -j "$jobs" -f "$here/Makefile" OUT="$out" OBJDIR="$objdir" ${HIPCC:+HIPCC="$HIPCC"}
 grep -h -E "warning" "$objdir"/*.remarks | grep -v "Rpass" | head -20 || true
 # (kernels of this library only: the rocPRIM sort / scan kernels dgn_graph_build.hip instantiates are the library's business)
 scratch="$(grep -h -B8 -E "ScratchSize \[bytes/lane\]: [1-9]" "$objdir"/*.remarks | grep -E "Function Name" | grep -v -E "rocprim|hipcub" || true)"

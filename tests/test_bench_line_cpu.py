@@ -41,3 +41,27 @@ def test_compact_line_sheds_fields_rather_than_overflow():
     rec = b.compact_line(full)
     assert len(json.dumps(rec)) < 4096
     assert "roofline" in rec and "cpu_baseline" in rec and "value" in rec
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget():
+    """--dump-outputs: arrays over the budget come out as the same seeded row sample on every call (with their row indices), small
+    arrays whole, non-float tensors left out, everything together within DUMP_BYTES (under 64 MB)."""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(0)
+    named = {"out": torch.randn(300_000, 70, generator=g), "h.grad": torch.randn(300_000, 70, generator=g),
+             "w.grad": torch.randn(70, 70, generator=g), "bn.num_batches_tracked": torch.tensor(3), "none.grad": None}
+    a1, a2 = b.snapshot_outputs(named), b.snapshot_outputs(named)
+    assert set(a1) == {"out", "out_rows", "h.grad", "h.grad_rows", "w.grad"}
+    assert sum(a.nbytes for a in a1.values()) <= b.DUMP_BYTES < 64e6
+    for k in a1:
+        assert a1[k].dtype in (np.float32, np.float64), k
+        np.testing.assert_array_equal(a1[k], a2[k])
+    rows = a1["out_rows"].astype(np.int64)
+    assert len(rows) > 10_000 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(a1["out"], named["out"].numpy()[rows])
+    np.testing.assert_array_equal(a1["h.grad_rows"], a1["out_rows"])
+    np.testing.assert_array_equal(a1["w.grad"], named["w.grad"].numpy())
+    whole = b.snapshot_outputs({"out": named["out"][:1000]})
+    assert set(whole) == {"out"} and whole["out"].shape == (1000, 70)

@@ -14,7 +14,8 @@ for n_graphs in (128, 256, 512, 1024, 1400):
         ops.BLOCK_LAYER_MAX_NODES = lim
         wl = copy.deepcopy(bench.WORKLOADS[base])
         wl["gen"] = (wl["gen"][0], dict(wl["gen"][1], n_graphs=n_graphs))
-        args = argparse.Namespace(steps=100, warmup=20, hipgraph=True, scaling=None, workload=base, no_cpu_baseline=True, aggregators=None, scalers=None)
+        args = argparse.Namespace(steps=100, warmup=20, hipgraph=True, scaling=None, workload=base, no_cpu_baseline=True, aggregators=None, scalers=None,
+                                  full=False, dump_outputs=None)
         r, _ = bench.run_layer_workload(args, wl, 0, 1, dev, steps=100, warmup=20, tag=None)
         out.append(r["ms_per_step"])
     print(f"{base} x {n_graphs} graphs ({r['nodes_per_rank']} nodes): block route {out[0]:.4f} ms, streaming {out[1]:.4f} ms", flush=True)
