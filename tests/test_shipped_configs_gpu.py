@@ -35,40 +35,71 @@ def _check_grad(a, r32, r64, name, strict=True):
     assert float((a - r64).abs().max()) <= 10 * 2e-5 * scale + 4 * float((r32 - r64).abs().max()), f"{name}: not close to the fp64 evaluation"
 
 
+def _o1_layer(type_net, hidden, aggs, scalers, graph_norm, towers, b):
+    """The layer on the CPU with O(1) weights -- the reference's init (gain 1/in_size) makes layer outputs ~1e-3 and hides errors (SURVEY
+    appendix B #5) -- and h, cotangent ~ N(0, 1) from a CPU generator: (layer, avg_log, h, cotangent)."""
+    import dgn_amd
+    N = int(b["num_nodes"])
+    avg = float(torch.log(torch.bincount(b["dst"], minlength=N).float() + 1).mean())
+    torch.manual_seed(0)
+    kw = dict(towers=towers) if type_net == "towers" else {}
+    layer = dgn_amd.DGNLayer(hidden, hidden, 0.0, graph_norm, True, aggs, scalers, {"log": torch.tensor(avg)}, type_net, True,
+                             edge_features=False, edge_dim=0, **kw).model
+    gen = torch.Generator().manual_seed(1)
+    with torch.no_grad():
+        for p in layer.parameters():
+            if p.dim() == 2 and type_net != "towers":
+                p.copy_(torch.randn(p.shape, generator=gen) / p.shape[1] ** 0.5)
+            else:          # (biases and BatchNorm's affine pair; towers: every parameter, the default init plus N(0, 0.1))
+                p.add_(0.1 * torch.randn(p.shape, generator=gen))
+    return layer, avg, torch.randn(N, hidden, generator=gen), torch.randn(N, hidden, generator=gen)
+
+
+def _oracle_of(layer, type_net, aggs, scalers, avg, graph_norm, towers, b, h, ct):
+    """``oracle(dtype, keep_graph=False)`` -> (y, [d h] + parameter gradients, parameter names, BatchNorm running statistics, again):
+    the oracle's layer step on the layer's state.  With ``keep_graph`` the autograd graph is retained and ``again(cotangent)`` pulls
+    another cotangent back through it (the gradient is linear in the cotangent); ``again`` is None otherwise."""
+    from oracle import dgn_oracle as orc
+    N = int(b["num_nodes"])
+
+    def oracle(dtype, keep_graph=False):
+        sd = {k: (v.detach().to(dtype).requires_grad_("running" not in k) if v.dtype.is_floating_point else v.clone())
+              for k, v in layer.state_dict().items()}
+        names = [k for k, v in sd.items() if v.dtype.is_floating_point and v.requires_grad]
+        cfg = dict(aggregators=aggs, scalers=scalers, avg_log=torch.tensor(avg, dtype=dtype), graph_norm=graph_norm, batch_norm=True,
+                   residual=True, towers=towers, divide_input=True, edge_features=False)
+        hh = h.to(dtype).requires_grad_(True)
+        y, stats = orc.layer_forward(type_net, sd, cfg, b["src"], b["dst"], N, b["eig"].to(dtype), hh, None, b["snorm_n"].to(dtype), training=True)
+        wrt = [hh] + [sd[k] for k in names]
+        again = (lambda c: torch.autograd.grad(y, wrt, c.to(dtype), retain_graph=True)) if keep_graph else None
+        return y, torch.autograd.grad(y, wrt, ct.to(dtype), retain_graph=keep_graph), names, stats, again
+
+    return oracle
+
+
+def _check_running_stats(layer, stats):
+    """BatchNorm running statistics of every BatchNorm module against the oracle's; one batch counted."""
+    sd = layer.state_dict()
+    assert stats and len(stats) == 2 * sum(isinstance(m, torch.nn.BatchNorm1d) for m in layer.modules()), sorted(stats)
+    for k, v in stats.items():
+        np.testing.assert_allclose(sd[k].cpu().numpy(), v.numpy(), rtol=1e-5, atol=1e-6, err_msg=k)
+    for k, v in sd.items():
+        if k.endswith("num_batches_tracked"):
+            assert int(v) == 1, k
+
+
 def _layer_vs_oracle(monkeypatch, type_net, F_, aggs, scalers, graph_norm, batch, min_rows, strict=True):
     import dgn_amd
-    from oracle import dgn_oracle as orc
     if min_rows is not None:
         monkeypatch.setattr(dgn_amd.ops, "LINEAR_MIN_ROWS", min_rows)
         monkeypatch.setattr(dgn_amd.ops, "WIDE_MIN_ROWS", min_rows)
         monkeypatch.setattr(dgn_amd.ops, "WHOLE_LAYER_MIN_ROWS", min_rows)      # (1 << 40: the per-op route on the library's GEMMs)
     dev = torch.device("cuda")
     src, dst, N = batch["src"], batch["dst"], int(batch["num_nodes"])
-    avg = float(torch.log(torch.bincount(dst, minlength=N).float() + 1).mean())
-    torch.manual_seed(0)
-    layer = dgn_amd.DGNLayer(F_, F_, 0.0, graph_norm, True, aggs, scalers, {"log": torch.tensor(avg)}, type_net, True,
-                             edge_features=False, edge_dim=0).model
-    gen = torch.Generator().manual_seed(1)
-    with torch.no_grad():          # O(1) weights: the reference's init (gain 1/in_size) makes layer outputs ~1e-3
-        for p in layer.parameters():
-            if p.dim() == 2:
-                p.copy_(torch.randn(p.shape, generator=gen) / p.shape[1] ** 0.5)
-            else:
-                p.add_(0.1 * torch.randn(p.shape, generator=gen))
-    h, ct = torch.randn(N, F_, generator=gen), torch.randn(N, F_, generator=gen)
-
-    def oracle(dtype):
-        sd = {k: (v.detach().to(dtype).requires_grad_("running" not in k) if v.dtype.is_floating_point else v.clone())
-              for k, v in layer.state_dict().items()}
-        names = [k for k, v in sd.items() if v.dtype.is_floating_point and v.requires_grad]
-        cfg = dict(aggregators=aggs, scalers=scalers, avg_log=torch.tensor(avg, dtype=dtype), graph_norm=graph_norm, batch_norm=True,
-                   residual=True, towers=1, divide_input=True, edge_features=False)
-        hh = h.to(dtype).requires_grad_(True)
-        y, stats = orc.layer_forward(type_net, sd, cfg, src, dst, N, batch["eig"].to(dtype), hh, None, batch["snorm_n"].to(dtype), training=True)
-        return y, torch.autograd.grad(y, [hh] + [sd[k] for k in names], ct.to(dtype)), names, stats
-
-    y32, g32, names, stats = oracle(torch.float32)
-    y64, g64, _, _ = oracle(torch.float64)
+    layer, avg, h, ct = _o1_layer(type_net, F_, aggs, scalers, graph_norm, 1, batch)
+    oracle = _oracle_of(layer, type_net, aggs, scalers, avg, graph_norm, 1, batch, h, ct)
+    y32, g32, names, stats, _ = oracle(torch.float32)
+    y64, g64, _, _, _ = oracle(torch.float64)
     layer = layer.to(dev).train()
     graph = dgn_amd.DGNGraph(src.to(dev), dst.to(dev), N, eig=batch["eig"].to(dev))
     hd = h.to(dev).requires_grad_(True)
@@ -79,8 +110,7 @@ def _layer_vs_oracle(monkeypatch, type_net, F_, aggs, scalers, graph_norm, batch
     check(y, y32, y64, f"{type_net} F={F_} y", rtol=2e-5, atol=2e-5, abs_scale=1.0, max_escape_fraction=0.0)
     for a, r32, r64, k in zip(gd, g32, g64, ["h"] + names):
         _check_grad(a, r32, r64, k, strict=strict)
-    for k, v in stats.items():
-        np.testing.assert_allclose(layer.state_dict()[k].cpu().numpy(), v.numpy(), rtol=1e-5, atol=1e-6, err_msg=k)
+    _check_running_stats(layer, stats)
 
 
 ROUTES = pytest.mark.parametrize("min_rows", [0, 1 << 40], ids=["own-kernels", "library-gemm"])
@@ -157,32 +187,13 @@ def test_towers_layer_odd_tower_width_vs_oracle(monkeypatch, hidden, towers):
 
 def _towers_vs_oracle(monkeypatch, hidden, towers, b):
     import dgn_amd
-    from oracle import dgn_oracle as orc
     dev = torch.device("cuda")
     src, dst, N = b["src"], b["dst"], int(b["num_nodes"])
     aggs, scalers = "mean max min dir1-av dir1-dx", "identity amplification attenuation"
-    avg = float(torch.log(torch.bincount(dst, minlength=N).float() + 1).mean())
-    torch.manual_seed(0)
-    layer = dgn_amd.DGNLayer(hidden, hidden, 0.0, True, True, aggs, scalers, {"log": torch.tensor(avg)}, "towers", True, towers=towers,
-                             edge_features=False, edge_dim=0).model
-    gen = torch.Generator().manual_seed(1)
-    with torch.no_grad():
-        for p in layer.parameters():
-            p.add_(0.1 * torch.randn(p.shape, generator=gen))
-    h, ct = torch.randn(N, hidden, generator=gen), torch.randn(N, hidden, generator=gen)
-
-    def oracle(dtype):
-        sd = {k: (v.detach().to(dtype).requires_grad_("running" not in k) if v.dtype.is_floating_point else v.clone())
-              for k, v in layer.state_dict().items()}
-        names = [k for k, v in sd.items() if v.dtype.is_floating_point and v.requires_grad]
-        cfg = dict(aggregators=aggs, scalers=scalers, avg_log=torch.tensor(avg, dtype=dtype), graph_norm=True, batch_norm=True,
-                   residual=True, towers=towers, divide_input=True, edge_features=False)
-        hh = h.to(dtype).requires_grad_(True)
-        y, _ = orc.layer_forward("towers", sd, cfg, src, dst, N, b["eig"].to(dtype), hh, None, b["snorm_n"].to(dtype), training=True)
-        return y, torch.autograd.grad(y, [hh] + [sd[k] for k in names], ct.to(dtype)), names
-
-    y32, g32, names = oracle(torch.float32)
-    y64, g64, _ = oracle(torch.float64)
+    layer, avg, h, ct = _o1_layer("towers", hidden, aggs, scalers, True, towers, b)
+    oracle = _oracle_of(layer, "towers", aggs, scalers, avg, True, towers, b, h, ct)
+    y32, g32, names, stats, _ = oracle(torch.float32)
+    y64, g64, _, _, _ = oracle(torch.float64)
     layer = layer.to(dev).train()
     graph = dgn_amd.DGNGraph(src.to(dev), dst.to(dev), N, eig=b["eig"].to(dev))
     hd = h.to(dev).requires_grad_(True)
@@ -192,6 +203,7 @@ def _towers_vs_oracle(monkeypatch, hidden, towers, b):
     np.testing.assert_allclose(y.detach().cpu().numpy(), y32.detach().numpy(), rtol=2e-5, atol=2e-5)
     for a, r32, r64, k in zip(gd, g32, g64, ["h"] + names):
         _check_grad(a, r32, r64, k)
+    _check_running_stats(layer, stats)          # (the five per-tower BatchNorms)
 
 
 def test_c4_at_the_default_threshold_takes_the_degree_class_route_vs_oracle(monkeypatch):
@@ -219,8 +231,9 @@ def test_molecule_batches_between_the_dispatch_thresholds_at_the_library_default
     """the gaps between the dispatch thresholds at the LIBRARY'S DEFAULTS (tests/conftest.py lowers three of them for
     the rest of the suite).  A molecule batch above the graph-block route (8 192 nodes) and below the block backward (131 072 nodes) runs
     the STAGED backward sweep (agg_bwd_short + seg_sum_rows); below 16 384 nodes posttrans is the folded product, above it one product per
-    in-degree class.  BASELINE C4's layer on (a) ~11.5 k nodes: folded posttrans + staged backward, (b) C4's own batch (2048 graphs,
-    ~52 k nodes: what bench.py's c4 leg runs): degree-class posttrans + staged backward -- values and every gradient vs the oracle."""
+    in-degree class.  BASELINE C4's layer on (a) 450 graphs, ~11.5 k nodes: folded posttrans + staged backward, (b) 720 graphs, ~18.4 k
+    nodes: degree-class posttrans + staged backward (the routes of bench.py's c4 leg; C4's OWN batch, 2048 graphs / 52 754 nodes, is
+    tests/test_bench_sizes_gpu.py) -- values and every gradient vs the oracle."""
     import dgn_amd
     from dgn_amd import _lib, synth
     monkeypatch.setattr(dgn_amd.ops, "DC_MIN_NODES", 16384)
