@@ -237,3 +237,71 @@ class CapturedNetStep:
         else:
             self.graph.replay()
         return self.loss
+
+
+class CapturedNodeStep:
+    """One captured HIP graph for the whole training step of the node-classification net (``dgn_amd.nets.DGNNodeNet``: embedding, L
+    layers, per-node MLP, batch-balanced cross-entropy with the confusion matrix of ``accuracy_sbm``, backward, Adam) at a fixed capacity:
+    ``load(batch)`` writes the batch into static buffers, ``step()`` is one graph launch and returns ``(loss, confusion)`` device tensors.
+
+    Padding: node rows beyond the batch are isolated (``PaddedBatch``) and carry the label -1 -- the loss kernel counts them nowhere and
+    writes zero gradient rows for them, which is the zero cotangent ``PaddedBatch`` asks for; no readout CSR and no graph rows are needed.
+
+    ``optimizer``: as for ``CapturedNetStep`` (capturable, built on parameters that never took part in a default-stream autograd pass);
+    by default the net's Parameter objects are re-created (``rewrap_parameters``) and a capturable Adam is built on them."""
+
+    def __init__(self, net, n_cap: int, e_cap: int, eig_dim: int, lr: float = 1e-3, optimizer=None, device=None):
+        dev = torch.device(device if device is not None else next(net.parameters()).device)
+        if getattr(net, "edge_feat", False):
+            raise ValueError("CapturedNodeStep: nets with edge_feat=True are not supported (no static edge-feature buffer)")
+        if getattr(net, "pos_enc_dim", 0) > 0:
+            raise ValueError("CapturedNodeStep: nets with pos_enc_dim > 0 are not supported (no static positional-encoding buffer)")
+        self.net, self.device = net, dev
+        self.n_classes = int(net.n_classes)
+        self.pb = PaddedBatch(n_cap, e_cap, dev, eig_dim)
+        self.feats = torch.zeros(n_cap, dtype=torch.int64, device=dev)
+        self.snorm = self.pb.add_node_tensor("snorm", 1)
+        self.labels = torch.full((n_cap,), -1, dtype=torch.int64, device=dev)
+        self.loss = torch.zeros((), device=dev)
+        self.confusion = torch.zeros(self.n_classes, self.n_classes, dtype=torch.int64, device=dev)
+        if optimizer is None:
+            rewrap_parameters(net)
+            try:
+                optimizer = torch.optim.Adam(net.parameters(), lr=lr, capturable=True, fused=True)
+            except Exception:
+                optimizer = torch.optim.Adam(net.parameters(), lr=lr, capturable=True)
+        self.opt = optimizer
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+
+    @torch.no_grad()
+    def load(self, src, dst, num_nodes: int, eig, feats, snorm, labels, sizes=None) -> None:
+        """feats [num_nodes] int64 node types, labels [num_nodes] int64 classes; sizes: nodes per graph (only for a graph with a block table)."""
+        num_nodes = int(num_nodes)
+        self.pb.load(src, dst, num_nodes, eig, node={"snorm": snorm}, graph_sizes=sizes)
+        self.feats[:num_nodes].copy_(feats, non_blocking=True)
+        self.feats[num_nodes:].zero_()
+        self.labels[:num_nodes].copy_(labels, non_blocking=True)
+        self.labels[num_nodes:].fill_(-1)
+
+    def _step(self) -> None:
+        self.opt.zero_grad(set_to_none=True)
+        self.pb.graph.invalidate_caches()
+        scores = self.net(self.pb.graph, self.feats, None, self.snorm, None)
+        loss, cm = self.net.loss(scores, self.labels, confusion=True)
+        loss.backward()
+        self.opt.step()
+        self.loss.copy_(loss.detach())
+        self.confusion.copy_(cm)
+        del scores, loss, cm
+
+    def capture(self, warmup: int = 3) -> None:
+        """Capture the step on the batch currently loaded (the warm-up steps DO update the parameters)."""
+        self.graph = capture(self._step, warmup=warmup)
+
+    def step(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One training step on the loaded batch; returns the (device) loss and confusion matrix of that step."""
+        if self.graph is None:
+            self._step()
+        else:
+            self.graph.replay()
+        return self.loss, self.confusion

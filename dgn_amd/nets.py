@@ -1,5 +1,6 @@
-"""Host-side mirror of the reference's graph-regression net (the direct caller of the layer):
-``realworld_benchmark/nets/molecules_graph_regression/dgn_net.py:8-95`` (DGNNet) and ``nets/mlp_readout_layer.py:13-32`` (MLPReadout).
+"""Host-side mirrors of the reference's nets (the direct callers of the layer): graph regression,
+``realworld_benchmark/nets/molecules_graph_regression/dgn_net.py:8-95`` (DGNNet) and ``nets/mlp_readout_layer.py:13-32`` (MLPReadout); node
+classification on SBM graphs, ``nets/SBMs_node_classification/dgn_net.py:8-81`` (DGNNodeNet, at the end of this file, with ``accuracy_sbm``).
 
 Same constructor dictionary, ``forward(g, h, e, snorm_n, snorm_e)``, ``loss`` and ``state_dict`` keys (a reference checkpoint loads
 as is); no DGL call: the layers are ``dgn_amd.DGNLayer``, the readouts ``dgn_amd.readout``, and with ``edge_feat`` the bond-type
@@ -95,3 +96,54 @@ class DGNNet(nn.Module):
 
     def loss(self, scores, targets):
         return F.l1_loss(scores, targets)
+
+
+class DGNNodeNet(nn.Module):
+    """Mirror of the reference's node-classification net (``nets/SBMs_node_classification/dgn_net.py:8-65``: PATTERN / CLUSTER): node-type
+    embedding, ``L`` DGN layers, a per-node ``MLPReadout`` to ``n_classes`` scores.  Same constructor dictionary, ``forward`` signature and
+    ``state_dict`` keys (``embedding_h``, optional ``embedding_pos_enc``, ``layers.{i}.*``, ``MLP_layer.FC_layers.{i}.*``).  ``loss`` is the
+    reference's batch-balanced cross-entropy (:67-81) as ``ops.balanced_cross_entropy``: three launches, no host read-back.  The MLP head
+    stays on torch's GEMMs (widths such as 47 -> 23 -> 11 -> 2 are outside the tall-skinny Linear's shapes).  Parity: fixture G11
+    (tests/golden/make_golden_node.py), produced by the unmodified reference net."""
+
+    def __init__(self, net_params: dict):
+        super().__init__()
+        p = net_params
+        hidden, out_dim, n_layers = p["hidden_dim"], p["out_dim"], p["L"]
+        self.type_net, self.pos_enc_dim, self.readout = p["type_net"], p["pos_enc_dim"], p["readout"]
+        self.edge_feat, self.device, self.n_classes = p["edge_feat"], p["device"], p["n_classes"]
+        if self.pos_enc_dim > 0:
+            self.embedding_pos_enc = nn.Linear(self.pos_enc_dim, hidden)
+        self.embedding_h = nn.Embedding(p["in_dim"], hidden)
+        self.in_feat_dropout = nn.Dropout(p["in_feat_dropout"])
+        make = lambda o: DGNLayer(in_dim=hidden, out_dim=o, dropout=p["dropout"], graph_norm=p["graph_norm"], batch_norm=p["batch_norm"],
+                                  residual=p["residual"], aggregators=p["aggregators"], scalers=p["scalers"], avg_d=p["avg_d"],
+                                  type_net=self.type_net, edge_features=self.edge_feat, edge_dim=p["edge_dim"],
+                                  pretrans_layers=p["pretrans_layers"], posttrans_layers=p["posttrans_layers"]).model
+        self.layers = nn.ModuleList([make(hidden) for _ in range(n_layers - 1)] + [make(out_dim)])
+        self.MLP_layer = MLPReadout(out_dim, self.n_classes)
+
+    def forward(self, g, h, e, snorm_n, snorm_e=None):
+        h = self.in_feat_dropout(small_table_embedding(self.embedding_h, h))
+        if self.pos_enc_dim > 0:
+            h = h + self.embedding_pos_enc(g.ndata["pos_enc"].to(h.device))
+        for conv in self.layers:
+            h = conv(g, h, e, snorm_n)
+        return self.MLP_layer(h)
+
+    def loss(self, pred, label, confusion: bool = False):
+        """``label < 0`` marks a padding row.  ``confusion=True``: ``(loss, [C, C] int64 device matrix)`` for ``accuracy_sbm``."""
+        from .ops import balanced_cross_entropy
+        return balanced_cross_entropy(pred, label, self.n_classes, confusion=confusion)
+
+
+def accuracy_sbm(confusion: torch.Tensor) -> torch.Tensor:
+    """The reference's ``accuracy_SBM`` (train/metrics.py:41-53) from the confusion matrix of ``ops.balanced_cross_entropy`` (which holds the
+    reference's prediction rule), device ops only, a 0-dim float64 tensor: ``100 * sum_r recall_r / #{r: CM[r, r] > 0}`` over the classes
+    present among the labels.  No class with a hit: 0 (the reference divides by zero).  Matrices of several batches may be added up first;
+    the reference averages per-batch accuracies instead, so add up accuracies to reproduce its epoch figure."""
+    cm = confusion.to(torch.float64)
+    count, hit = cm.sum(1), cm.diagonal()
+    recall = hit / count.clamp_min(1.0)                   # (an absent class has no hit either: 0 / 1)
+    scored = (hit > 0).sum()
+    return 100.0 * recall.sum() / scored.clamp_min(1)     # (no class with a hit: 0 / 1)

@@ -1878,3 +1878,59 @@ class _AssembleOperands(torch.autograd.Function):
 def assemble_operands(maps, params):
     """the operand tensors (views of one buffer, in the order of maps["op_sizes"] / maps["op_shapes"])"""
     return _AssembleOperands.apply(maps, *params)
+
+
+class _BalancedCrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, labels, n_classes, want_confusion):
+        lib = _lib.load()
+        if not scores.is_cuda:
+            raise _lib.DgnError("balanced_cross_entropy: CUDA tensors only (dgn_amd has no CPU path)")
+        if scores.dim() != 2 or scores.shape[1] != n_classes or scores.dtype != torch.float32:
+            raise ValueError(f"balanced_cross_entropy: scores must be float32 [N, {n_classes}], got {scores.dtype} {tuple(scores.shape)}")
+        if labels.dtype != torch.int64 or labels.shape != (scores.shape[0],):
+            raise ValueError("balanced_cross_entropy: labels must be int64 [N]")
+        if scores.stride(1) != 1:
+            scores = scores.contiguous()
+        labels = labels.contiguous()
+        N, dev = scores.shape[0], scores.device
+        want_grad = ctx.needs_input_grad[0]                   # (False under torch.no_grad(): no gradient buffer is written)
+        out = torch.empty(1 + n_classes, dtype=torch.float32, device=dev)           # [loss | weight]
+        g = torch.empty(N, n_classes, dtype=torch.float32, device=dev) if want_grad else None
+        cm = torch.empty(n_classes, n_classes, dtype=torch.int64, device=dev) if want_confusion else None
+        ws_bytes = lib.dgn_node_ce_workspace_bytes(N, n_classes)
+        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
+        rc = lib.dgn_node_ce_forward(N, n_classes, scores.data_ptr(), scores.stride(0) if N > 1 else n_classes, labels.data_ptr(), out.data_ptr(),
+                                     out.data_ptr() + 4, _ptr(g), n_classes, _ptr(cm), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        _lib.check(rc, "dgn_node_ce_forward")
+        ctx.save_for_backward(g)
+        ctx.n_classes = n_classes
+        ctx.set_materialize_grads(False)                      # (no zero-filled gradient for the integer matrix: the backward is ONE launch)
+        loss = out[0]
+        if want_confusion:
+            ctx.mark_non_differentiable(cm)
+            return loss, cm
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss, *_):
+        (g,) = ctx.saved_tensors
+        if g_loss is None:
+            return None, None, None, None
+        lib = _lib.load()
+        g_loss = g_loss.to(torch.float32).contiguous()
+        out = torch.empty_like(g)
+        rc = lib.dgn_node_ce_backward(g.shape[0], ctx.n_classes, g.data_ptr(), g.stride(0), g_loss.data_ptr(), out.data_ptr(), out.stride(0),
+                                      _lib.stream_ptr(g.device))
+        _lib.check(rc, "dgn_node_ce_backward")
+        return out, None, None, None
+
+
+def balanced_cross_entropy(scores: torch.Tensor, labels: torch.Tensor, n_classes: int, confusion: bool = False):
+    """The node-classification loss of the reference (nets/SBMs_node_classification/dgn_net.py:67-81): cross-entropy with the class weights
+    ``(V - count_c) / V`` of THIS batch's label counts (0 for an absent class), mean-reduced by the weights.  ``scores [N, n_classes]``
+    float32, ``labels [N]`` int64; a label < 0 marks a padding row (counts nowhere, zero gradient).  Three launches, no host read-back
+    (capturable).  Returns the 0-dim loss; with ``confusion=True`` also the ``[C, C]`` int64 device matrix of the reference's
+    ``accuracy_SBM`` (train/metrics.py:37-40: rows = label, columns = arg-max over classes of the softmax over the NODES), see
+    ``nets.accuracy_sbm``.  One class only among the labels: ``nan``, as the reference."""
+    return _BalancedCrossEntropy.apply(scores, labels, int(n_classes), bool(confusion))

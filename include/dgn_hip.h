@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DGN_ABI_VERSION 28
+#define DGN_ABI_VERSION 29
 
 #define DGN_MAX_AGG 16     /* aggregators per launch (the host splits longer lists)            */
 #define DGN_MAX_CH 4       /* edge-weight channels per launch                                   */
@@ -776,6 +776,30 @@ size_t dgn_block_layer_forward_workspace_bytes(const DgnBlockLayer* layer);
 int dgn_block_layer_forward(const DgnBlockLayer* layer, void* stream);
 size_t dgn_block_layer_backward_workspace_bytes(const DgnBlockLayer* layer);
 int dgn_block_layer_backward(const DgnBlockLayer* layer, const DgnBlockGrads* grads, void* stream);
+
+/* ---- node classification: balanced cross-entropy + the SBM confusion matrix (dgn_node_ce.hip) ------------------------------------
+ * Replaces DGNNet.loss of nets/SBMs_node_classification/dgn_net.py:67-81 (bincount -> nonzero -> unique -> indexed assignment ->
+ * CrossEntropyLoss(weight): ~20 launches and two device-to-host read-backs) and the prediction + confusion_matrix of accuracy_SBM
+ * (train/metrics.py:37-40, a host-side scikit-learn call per batch) by three launches on the caller's stream with nothing read back.
+ * scores [N, C] fp32 (row stride ld), labels [N] int64, 1 <= C <= 32, N < 2^31.  A label < 0 marks a row that does not exist
+ * (padding of a captured batch): it counts nowhere and its gradient row is zero; a label >= C is treated the same way (no access
+ * outside the tables).  V = number of valid rows, count[c] = valid rows labelled c:
+ *     weight[c]   = count[c] > 0 ? float(V - count[c]) / float(V) : 0                                   (dgn_net.py:74-75)
+ *     loss        = sum_n weight[y_n] (logsumexp_c scores[n, :] - scores[n, y_n]) / sum_c weight[c] count[c]   (:78-79, mean reduction)
+ *     g_scores    = d loss / d scores  [N, C] (row stride ld_g), written in the pass that forms the loss terms; NULL: not wanted
+ *     confusion   = [C, C] int64, rows = label, columns = argmax_c (scores[n, c] - logsumexp_{n' valid} scores[n', c]) -- the log form
+ *                   of metrics.py:39's Softmax(dim=0) (over the NODES) then argmax(axis=1), first maximum on ties; NULL: not wanted
+ * loss: DEVICE float, weight: DEVICE [C] or NULL.  With one class among the valid labels every weight is 0 and loss and the valid rows'
+ * gradients are nan (0 / 0), as the reference's; V == 0 (the reference raises): loss 0, gradients 0; n_rows == 0: loss 0.
+ * Reductions run in a fixed order without floating-point atomics: the same input gives the same bits.  ws: 8-byte aligned,
+ * dgn_node_ce_workspace_bytes(n_rows, n_classes) bytes (0 for arguments out of range).
+ * dgn_node_ce_backward: the autograd backward, ONE launch: g_scores[n, c] = g_saved[n, c] * *g_loss (g_loss: DEVICE float, the
+ * incoming gradient of the scalar loss; g_saved: what the forward wrote).                                                          */
+size_t dgn_node_ce_workspace_bytes(int64_t n_rows, int32_t n_classes);
+int dgn_node_ce_forward(int64_t n_rows, int32_t n_classes, const float* scores, int64_t ld, const int64_t* labels, float* loss,
+                        float* weight, float* g_scores, int64_t ld_g, int64_t* confusion, void* ws, size_t ws_bytes, void* stream);
+int dgn_node_ce_backward(int64_t n_rows, int32_t n_classes, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
+                         int64_t ld_out, void* stream);
 
 #ifdef __cplusplus
 }
