@@ -127,8 +127,8 @@ def _dropout(x, p, training):
 
 
 def _block_dropout(layer, h):
-    """``(p, key tensor, offset)`` for ops.block_layer when the layer's F.dropout is active (training, 0 < p < 1), else None: the graph-block
-    route draws the keep bits inside its tail kernels -- the bits ops.dropout would draw for the same key and offset."""
+    """``(p, key tensor, offset)`` for ops.block_layer / ops.towers_layer when the layer's F.dropout is active (training, 0 < p < 1), else
+    None: these routes draw the keep bits inside their tail kernels -- the bits ops.dropout would draw for the same key and offset."""
     if layer.training and 0 < layer.dropout < 1:
         seed, offset = _next_dropout_key(h.device)
         return (float(layer.dropout), seed, offset)
@@ -224,8 +224,7 @@ def _edge_term(graph: DGNGraph, e, w_edge):
     EdgeTypeFeatures -- the [K, F] table and the slots' types."""
     if isinstance(e, EdgeTypeFeatures):
         Fm = w_edge.shape[0]
-        det = (Fm % 2 == 0) if _ops.DETERMINISTIC_BACKWARD == "auto" else bool(_ops.DETERMINISTIC_BACKWARD)
-        if e.table.shape[0] * Fm <= _ops.MAX_EDGE_TABLE and det and not hasattr(graph, "_pad"):
+        if e.table.shape[0] * Fm <= _ops.MAX_EDGE_TABLE and _ops._two_phase_scatter(Fm) and not hasattr(graph, "_pad"):
             return F.linear(e.table, w_edge), e.slot_types(graph)
         e = e.dense()
     # the permuted copy is edge_dim floats per edge (40 B), the product runs on the streaming Linear kernels (k = edge_dim)
@@ -301,22 +300,6 @@ def _folded_weight(w_agg, w_h, S, id_slot):
     return torch.cat([w, hcols], dim=2).reshape(S * fo, K + w_h.shape[1])
 
 
-def _combine_and_tail(layer, z, sc, bias, snorm_n, h_in):
-    """scale_combine -> (BatchNorm -> ReLU -> residual) of the simple / complex layers; one autograd node in training."""
-    row_scale = snorm_n if layer.graph_norm else None
-    res = h_in if layer.residual else None
-    bn = layer.batchnorm_h
-    width = z.shape[0] * (z.shape[2] // (sc.shape[1] if sc is not None else 1))
-    if layer.batch_norm and layer.training and bn_tail_supported([bn], z, True, width):
-        return combine_bn_tail(z, sc, bias, row_scale, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                               bn.momentum, bn.eps, relu=True, residual=res)
-    h = scale_combine(z, sc, bias, row_scale)
-    if layer.batch_norm:
-        return bn_tail(h, bn, layer.training, relu=True, residual=res)
-    h = F.relu(h)
-    return h_in + h if layer.residual else h
-
-
 def _pad_blocks(weight, n_blocks, F0, Fp):
     """[fo, n_blocks*F0] -> [fo, n_blocks*Fp]: a zero column after every F0-wide block (the padded feature)."""
     if Fp == F0:
@@ -341,16 +324,105 @@ def _block_route_ok(layer, h) -> bool:
             and layer.batch_norm and h.is_cuda
             and h.dtype == torch.float32 and h.dim() == 2
             and 0 < h.shape[0] <= (_ops.BLOCK_LAYER_MAX_NODES if layer.training else max(_ops.BLOCK_LAYER_MAX_NODES, _ops.BLOCK_LAYER_EVAL_MAX_NODES))
-            and all(bn.momentum is not None and bn.track_running_stats and bn.affine and not _ops._spans_ranks(bn, layer.training)
-                    for bn in _bns_of(layer)))
+            and all(_ops._bn_fusable(bn, layer.training) for bn in _bns_of(layer)))
 
 
 def _bns_of(layer):
     return [t.batchnorm_h for t in layer.towers] if hasattr(layer, "towers") else [layer.batchnorm_h]
 
 
-class DGNLayerSimple(nn.Module):
+class _Layer(nn.Module):
+    """``forward`` of the three layer types (registers nothing: the subclasses' state_dict is the reference's)."""
+
+    def forward(self, g, h, e, snorm_n):
+        # (a batch padded to a fixed row capacity carries its valid-row count as a device scalar: BatchNorm must know, ops.padded_rows)
+        with _ops.padded_rows(getattr(g, "n_valid", None)):
+            return self._forward(g, h, e, snorm_n)
+
+
+class _SingleLayer(_Layer):
+    """What DGNLayerSimple and DGNLayerComplex share: the order of the routes, the two fused routes (whose entry points take both layers
+    as ``type`` 0 / 1) and the tail.  A subclass states ``_TYPE_NET``, ``_WHOLE_PLAN`` (the attribute holding the whole-layer call's sweep
+    list), ``_fused_pretrans`` and its own message path, ``_per_op_forward``."""
+
+    def _forward(self, g, h, e, snorm_n):
+        y = self._block_layer(g, h, snorm_n)
+        if y is not None:
+            return y                                              # (dropout included)
+        y = self._whole_layer(g, h, snorm_n)
+        if y is not None:
+            return _dropout(y, self.dropout, self.training)       # (nets/dgn_layer.py:130, :201: the layer's last op)
+        return self._per_op_forward(g, h, e, snorm_n)
+
+    def _whole_layer(self, g, h, snorm_n):
+        """The layer through dgn_dense_layer_forward / _backward (one C call per direction), or None outside that entry point's domain
+        (training-mode BatchNorm, single-affine posttrans, what ``_fused_pretrans`` adds, enough rows for this library's own GEMM
+        kernels; the dropout follows the call)."""
+        bn = self.batchnorm_h
+        if not (_ops.WHOLE_LAYER and self.training and torch.is_grad_enabled() and self.batch_norm and h.is_cuda
+                and h.dtype == torch.float32 and h.dim() == 2 and h.shape[0] >= _ops.WHOLE_LAYER_MIN_ROWS and self.posttrans.is_single_affine()
+                and bn_tail_supported([bn], h, True, bn.num_features)):
+            return None
+        ok, pre, id_slot = self._fused_pretrans(False)
+        if not ok:
+            return None
+        lin, plan = self.posttrans.fully_connected[0].linear, getattr(self, self._WHOLE_PLAN)
+        S, A = self.plan.n_scalers, len(self.aggregators)
+        if len(plan.launches) != 1 or not _ops.dense_layer_supported(self._TYPE_NET, h.shape[1], lin.weight.shape[0], S, A):
+            return None
+        eig = g.ndata["eig"]
+        graph = as_dgn_graph(g, h.device)
+        if _ops.split_training_route(graph, S):
+            return None      # (hub rows: the per-op route runs posttrans per in-degree class + the folded product on the hubs alone)
+        sc = _scale_table(graph, self.plan.applied_scalers, self._avg_log) if S > 1 else None
+        return _ops.dense_layer(graph, plan, self._avg_log, graph.edge_weights(plan, eig), h, snorm_n if self.graph_norm else None, sc, bn,
+                                None if pre is None else pre.weight, None if pre is None else pre.bias, lin.weight, lin.bias, self._TYPE_NET, A,
+                                id_slot, self.residual)
+
+    def _block_layer(self, g, h, snorm_n):
+        """The layer on the graph-block route (ops.block_layer: batches at the reference's batch size), or None."""
+        bn, lin = self.batchnorm_h, self.posttrans.fully_connected[0].linear
+        if not (_block_route_ok(self, h) and self.posttrans.is_single_affine() and lin.bias is not None and 0 <= self.dropout < 1):
+            return None
+        ok, pre, _ = self._fused_pretrans(True)
+        if not ok:
+            return None
+        graph = as_dgn_graph(g, h.device)
+        if not _ops.block_layer_supported(graph, self.plan, self._TYPE_NET, 1, h.shape[1], lin.weight.shape[0], eval_only=not self.training):
+            return None
+        drop = _block_dropout(self, h)      # the layer's last op (nets/dgn_layer.py:130, :201) inside the route's tail kernels
+        params = (lin.weight, lin.bias, bn.weight, bn.bias) if pre is None else (pre.weight, pre.bias, lin.weight, lin.bias, bn.weight, bn.bias)
+        y = _ops.block_layer(graph, self.plan, self._avg_log, g.ndata["eig"], h, snorm_n if self.graph_norm else None, bn.running_mean, bn.running_var,
+                             bn.num_batches_tracked, params, self._TYPE_NET, 1, h.shape[1], lin.weight.shape[0], self.residual, bn.momentum, bn.eps,
+                             training=self.training, dropout=drop)
+        if drop is not None:
+            _dropout_key_used(drop[1])
+        return y
+
+    def _tail(self, h, h_in):
+        """BatchNorm -> ReLU -> residual -> dropout (nets/dgn_layer.py:123-130, :194-201)."""
+        if self.batch_norm:
+            h = bn_tail(h, self.batchnorm_h, self.training, relu=True, residual=h_in if self.residual else None)
+        else:
+            h = F.relu(h)
+            h = h_in + h if self.residual else h
+        return _dropout(h, self.dropout, self.training)
+
+    def _combine_and_tail(self, z, sc, bias, snorm_n, h_in):
+        """scale_combine -> the tail; combine and BatchNorm -> ReLU -> residual are one autograd node in training."""
+        row_scale = snorm_n if self.graph_norm else None
+        bn = self.batchnorm_h
+        width = z.shape[0] * (z.shape[2] // (sc.shape[1] if sc is not None else 1))
+        if self.batch_norm and self.training and bn_tail_supported([bn], z, True, width):
+            h = combine_bn_tail(z, sc, bias, row_scale, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                bn.momentum, bn.eps, relu=True, residual=h_in if self.residual else None)
+            return _dropout(h, self.dropout, self.training)
+        return self._tail(scale_combine(z, sc, bias, row_scale), h_in)
+
+
+class DGNLayerSimple(_SingleLayer):
     """dgn_layer.py:135-202: message = h[src]; posttrans on the aggregation only."""
+    _TYPE_NET, _WHOLE_PLAN = 0, "_kplan"
 
     def __init__(self, in_dim, out_dim, dropout, graph_norm, batch_norm, aggregators, scalers, residual, avg_d,
                  posttrans_layers=1):
@@ -374,54 +446,11 @@ class DGNLayerSimple(nn.Module):
         graph = as_dgn_graph(g, h.device)
         return directional_aggregate(graph, plan or self.plan, self._avg_log, x_src=h, x_in=h, eig=eig)
 
-    def forward(self, g, h, e, snorm_n):
-        # (a batch padded to a fixed row capacity carries its valid-row count as a device scalar: BatchNorm must know, ops.padded_rows)
-        with _ops.padded_rows(getattr(g, "n_valid", None)):
-            return self._forward(g, h, e, snorm_n)
+    def _fused_pretrans(self, block_route):
+        """(the fused routes take the layer, its pretrans Linear, id_slot of ops.dense_layer): no pretrans, nothing to ask."""
+        return True, None, 0
 
-    def _whole_layer(self, g, h, snorm_n):
-        """The layer through dgn_dense_layer_forward / _backward (one C call per direction), or None outside that entry point's domain
-        (training-mode BatchNorm, single-affine posttrans, no dropout, enough rows for this library's own GEMM kernels)."""
-        bn = self.batchnorm_h
-        if not (_ops.WHOLE_LAYER and self.training and torch.is_grad_enabled() and self.batch_norm and h.is_cuda
-                and h.dtype == torch.float32 and h.dim() == 2 and h.shape[0] >= _ops.WHOLE_LAYER_MIN_ROWS and self.posttrans.is_single_affine()
-                and bn_tail_supported([bn], h, True, bn.num_features)):
-            return None
-        lin = self.posttrans.fully_connected[0].linear
-        S, A = self.plan.n_scalers, len(self.aggregators)
-        if len(self._kplan.launches) != 1 or not _ops.dense_layer_supported(0, h.shape[1], lin.weight.shape[0], S, A):
-            return None
-        eig = g.ndata["eig"]
-        graph = as_dgn_graph(g, h.device)
-        if _ops.split_training_route(graph, S):
-            return None      # (hub rows: the per-op route below runs posttrans per in-degree class + the folded product on the hubs alone)
-        sc = _scale_table(graph, self.plan.applied_scalers, self._avg_log) if S > 1 else None
-        return _ops.dense_layer(graph, self._kplan, self._avg_log, graph.edge_weights(self._kplan, eig), h, snorm_n if self.graph_norm else None, sc, bn,
-                                None, None, lin.weight, lin.bias, 0, A, 0, self.residual)
-
-    def _block_layer(self, g, h, snorm_n):
-        """The layer on the graph-block route (ops.block_layer: batches at the reference's batch size), or None."""
-        bn, lin = self.batchnorm_h, self.posttrans.fully_connected[0].linear
-        if not (_block_route_ok(self, h) and self.posttrans.is_single_affine() and lin.bias is not None and 0 <= self.dropout < 1):
-            return None
-        graph = as_dgn_graph(g, h.device)
-        if not _ops.block_layer_supported(graph, self.plan, 0, 1, h.shape[1], lin.weight.shape[0], eval_only=not self.training):
-            return None
-        drop = _block_dropout(self, h)      # the layer's last op (nets/dgn_layer.py:201) inside the route's tail kernels
-        y = _ops.block_layer(graph, self.plan, self._avg_log, g.ndata["eig"], h, snorm_n if self.graph_norm else None, bn.running_mean, bn.running_var,
-                             bn.num_batches_tracked, (lin.weight, lin.bias, bn.weight, bn.bias), 0, 1, h.shape[1], lin.weight.shape[0],
-                             self.residual, bn.momentum, bn.eps, training=self.training, dropout=drop)
-        if drop is not None:
-            _dropout_key_used(drop[1])
-        return y
-
-    def _forward(self, g, h, e, snorm_n):
-        y = self._block_layer(g, h, snorm_n)
-        if y is not None:
-            return y                                              # (dropout included)
-        y = self._whole_layer(g, h, snorm_n)
-        if y is not None:
-            return _dropout(y, self.dropout, self.training)       # (nets/dgn_layer.py:201: the layer's last op)
+    def _per_op_forward(self, g, h, e, snorm_n):
         h_in = h
         F0 = h.shape[1]
         # Odd widths (ZINC simple: 75, CIFAR10: 65) would run the sweep with 4-byte lanes, a second, nearly empty
@@ -444,17 +473,11 @@ class DGNLayerSimple(nn.Module):
                     sc = _scale_table(graph, self.plan.applied_scalers, self._avg_log)
                     h = _ops.dc_posttrans_split(graph, agg, lin.weight, lin.bias, sc, snorm_n if self.graph_norm else None, A, F0)
                     del agg
-                    if self.batch_norm:
-                        h = bn_tail(h, self.batchnorm_h, self.training, relu=True, residual=h_in if self.residual else None)
-                    else:
-                        h = F.relu(h)
-                        h = h_in + h if self.residual else h
-                    return _dropout(h, self.dropout, self.training)
+                    return self._tail(h, h_in)
                 w = _pad_blocks(lin.weight, S * A, F0, Fp).reshape(fo, S, A * Fp).permute(1, 0, 2).reshape(S * fo, A * Fp)
                 z = node_linear(agg, w)
                 sc = _scale_table(graph, self.plan.applied_scalers, self._avg_log)
-                h = _combine_and_tail(self, z.unsqueeze(0), sc, lin.bias, snorm_n, h_in)      # (+snorm, BatchNorm, ReLU, residual)
-                return _dropout(h, self.dropout, self.training)
+                return self._combine_and_tail(z.unsqueeze(0), sc, lin.bias, snorm_n, h_in)     # (+snorm, BatchNorm, ReLU, residual, dropout)
             else:
                 agg = self.aggregate(graph, hp, None, eig)                                    # [N, A*Fp] (single scaler: not applied)
                 h = node_linear(agg, _pad_blocks(lin.weight, A, F0, Fp), lin.bias)
@@ -467,17 +490,12 @@ class DGNLayerSimple(nn.Module):
             h = self.posttrans(agg)
             if self.graph_norm:
                 h = h * snorm_n
-        if self.batch_norm:
-            h = bn_tail(h, self.batchnorm_h, self.training, relu=True, residual=h_in if self.residual else None)
-        else:
-            h = F.relu(h)
-            if self.residual:
-                h = h_in + h
-        return _dropout(h, self.dropout, self.training)
+        return self._tail(h, h_in)
 
 
-class DGNLayerComplex(nn.Module):
+class DGNLayerComplex(_SingleLayer):
     """dgn_layer.py:52-132: message = pretrans([h_src || h_dst (|| ef)]); posttrans on [h || agg]."""
+    _TYPE_NET, _WHOLE_PLAN = 1, "_kplan_x"
 
     def __init__(self, in_dim, out_dim, dropout, graph_norm, batch_norm, aggregators, scalers, avg_d, residual,
                  edge_features, edge_dim, pretrans_layers=1, posttrans_layers=1):
@@ -505,56 +523,15 @@ class DGNLayerComplex(nn.Module):
         return directional_aggregate(graph, plan or self.plan, self._avg_log, x_pair=x_pair, m_edge=m_edge,
                                      x_in=h, eig=eig, edge_type=edge_type)
 
-    def forward(self, g, h, e, snorm_n):
-        # (a batch padded to a fixed row capacity carries its valid-row count as a device scalar: BatchNorm must know, ops.padded_rows)
-        with _ops.padded_rows(getattr(g, "n_valid", None)):
-            return self._forward(g, h, e, snorm_n)
-
-    def _whole_layer(self, g, h, snorm_n):
-        """As DGNLayerSimple._whole_layer; additionally: single-affine pretrans, no edge features, identity among the applied scalers."""
-        bn = self.batchnorm_h
+    def _fused_pretrans(self, block_route):
+        """What the fused routes ask of the message path: a single-affine pretrans without edge features; the graph-block route reads
+        its bias, the whole-layer call needs the identity among the applied scalers (the slot the h block of posttrans acts through)."""
+        pre = self.pretrans.fully_connected[0].linear
         id_slot = _identity_slot(self.plan.applied_scalers)
-        if not (_ops.WHOLE_LAYER and self.training and torch.is_grad_enabled() and self.batch_norm and not self.edge_features
-                and h.is_cuda and h.dtype == torch.float32 and h.dim() == 2 and h.shape[0] >= _ops.WHOLE_LAYER_MIN_ROWS and id_slot is not None
-                and self.posttrans.is_single_affine() and self.pretrans.is_single_affine() and bn_tail_supported([bn], h, True, bn.num_features)):
-            return None
-        pre, lin = self.pretrans.fully_connected[0].linear, self.posttrans.fully_connected[0].linear
-        S, A = self.plan.n_scalers, len(self.aggregators)
-        if len(self._kplan_x.launches) != 1 or not _ops.dense_layer_supported(1, h.shape[1], lin.weight.shape[0], S, A):
-            return None
-        eig = g.ndata["eig"]
-        graph = as_dgn_graph(g, h.device)
-        if _ops.split_training_route(graph, S):
-            return None      # (hub rows: see DGNLayerSimple._whole_layer)
-        sc = _scale_table(graph, self.plan.applied_scalers, self._avg_log) if S > 1 else None
-        return _ops.dense_layer(graph, self._kplan_x, self._avg_log, graph.edge_weights(self._kplan_x, eig), h, snorm_n if self.graph_norm else None, sc,
-                                bn, pre.weight, pre.bias, lin.weight, lin.bias, 1, A, id_slot, self.residual)
+        ok = not self.edge_features and self.pretrans.is_single_affine() and (pre.bias is not None if block_route else id_slot is not None)
+        return ok, pre, id_slot
 
-    def _block_layer(self, g, h, snorm_n):
-        """As DGNLayerSimple._block_layer; additionally: single-affine pretrans with a bias, no edge features."""
-        bn = self.batchnorm_h
-        pre, lin = self.pretrans.fully_connected[0].linear, self.posttrans.fully_connected[0].linear
-        if not (_block_route_ok(self, h) and not self.edge_features and self.posttrans.is_single_affine() and self.pretrans.is_single_affine()
-                and lin.bias is not None and pre.bias is not None and 0 <= self.dropout < 1):
-            return None
-        graph = as_dgn_graph(g, h.device)
-        if not _ops.block_layer_supported(graph, self.plan, 1, 1, h.shape[1], lin.weight.shape[0], eval_only=not self.training):
-            return None
-        drop = _block_dropout(self, h)      # the layer's last op (nets/dgn_layer.py:130) inside the route's tail kernels
-        y = _ops.block_layer(graph, self.plan, self._avg_log, g.ndata["eig"], h, snorm_n if self.graph_norm else None, bn.running_mean, bn.running_var,
-                             bn.num_batches_tracked, (pre.weight, pre.bias, lin.weight, lin.bias, bn.weight, bn.bias), 1, 1, h.shape[1],
-                             lin.weight.shape[0], self.residual, bn.momentum, bn.eps, training=self.training, dropout=drop)
-        if drop is not None:
-            _dropout_key_used(drop[1])
-        return y
-
-    def _forward(self, g, h, e, snorm_n):
-        y = self._block_layer(g, h, snorm_n)
-        if y is not None:
-            return y                                              # (dropout included)
-        y = self._whole_layer(g, h, snorm_n)
-        if y is not None:
-            return _dropout(y, self.dropout, self.training)       # (nets/dgn_layer.py:130: the layer's last op)
+    def _per_op_forward(self, g, h, e, snorm_n):
         h_in = h
         eig = g.ndata["eig"]
         id_slot = _identity_slot(self.plan.applied_scalers)
@@ -580,28 +557,15 @@ class DGNLayerComplex(nn.Module):
                 h = _ops.dc_posttrans_split(graph, aggx, lin.weight, lin.bias, sc, snorm_n if self.graph_norm else None, len(self.aggregators), F0,
                                             id_slot=id_slot)
                 del aggx
-                if self.batch_norm:
-                    h = bn_tail(h, self.batchnorm_h, self.training, relu=True, residual=h_in if self.residual else None)
-                else:
-                    h = F.relu(h)
-                    h = h_in + h if self.residual else h
-                return _dropout(h, self.dropout, self.training)
+                return self._tail(h, h_in)
             w = _folded_weight(w_agg, w_h, S, id_slot)
             z = node_linear(aggx, w)
             sc = _scale_table(graph, self.plan.applied_scalers, self._avg_log)
-            h = _combine_and_tail(self, z.unsqueeze(0), sc, lin.bias, snorm_n, h_in)          # (+snorm, BatchNorm, ReLU, residual)
-            return _dropout(h, self.dropout, self.training)
-        else:
-            h = _posttrans_split(self.posttrans, h, self.aggregate(g, h, e, None, eig), self.in_dim)
-            if self.graph_norm:
-                h = h * snorm_n
-        if self.batch_norm:
-            h = bn_tail(h, self.batchnorm_h, self.training, relu=True, residual=h_in if self.residual else None)
-        else:
-            h = F.relu(h)
-            if self.residual:
-                h = h_in + h
-        return _dropout(h, self.dropout, self.training)
+            return self._combine_and_tail(z.unsqueeze(0), sc, lin.bias, snorm_n, h_in)        # (+snorm, BatchNorm, ReLU, residual, dropout)
+        h = _posttrans_split(self.posttrans, h, self.aggregate(g, h, e, None, eig), self.in_dim)
+        if self.graph_norm:
+            h = h * snorm_n
+        return self._tail(h, h_in)
 
 
 class DGNTower(nn.Module):
@@ -637,7 +601,7 @@ class DGNTower(nn.Module):
         return _dropout(h, self.dropout, self.training)
 
 
-class DGNLayerTower(nn.Module):
+class DGNLayerTower(_Layer):
     """dgn_layer.py:279-325."""
 
     def __init__(self, in_dim, out_dim, aggregators, scalers, avg_d, dropout, graph_norm, batch_norm, towers=5,
@@ -822,14 +786,7 @@ class DGNLayerTower(nn.Module):
                 w_edge = graph.edge_weights(self._kplan_x, g.ndata["eig"])
                 y = _ops.fused_sweep_posttrans_forward(graph, self._kplan_x, T, self._avg_log, w_edge, pq, x_in.contiguous(), ops["w"], sc, b_p,
                                                        row_scale)
-                if self.batch_norm:
-                    bns = [t.batchnorm_h for t in self.towers]
-                    if bn_tail_supported(bns, y, self.training):
-                        rm, rv, nbt = self._linked_bn_stats(y.device)
-                        y = bn_tail_fused(y, ops["bn_gamma"], ops["bn_beta"], rm, rv, nbt, bns[0].momentum, bns[0].eps, self.training)
-                    else:
-                        y = bn_tail(y, bns, self.training)
-                return _dropout(y, self.dropout, self.training)
+                return self._towers_tail(y, ops)
             aggx = directional_aggregate(graph, self._kplan_x, self._avg_log, x_pair=pq, m_edge=m_edge, x_in=x_in,
                                          eig=g.ndata["eig"], n_towers=T, tower_major=True, edge_type=edge_type)
             bns = [t.batchnorm_h for t in self.towers]
@@ -854,6 +811,10 @@ class DGNLayerTower(nn.Module):
             y = y + torch.bmm(x_in.view(N, T, fi).transpose(0, 1), ops["w_h"].transpose(1, 2)).transpose(0, 1).reshape(N, T * fo)
             if row_scale is not None:
                 y = y * row_scale
+        return self._towers_tail(y, ops)
+
+    def _towers_tail(self, y, ops):
+        """The towers' BatchNorms (channel-concatenated: one BatchNorm of width T * fo) and dropout on y [N, T * fo] (:272-275)."""
         if self.batch_norm:
             bns = [t.batchnorm_h for t in self.towers]
             if bn_tail_supported(bns, y, self.training):
@@ -886,10 +847,7 @@ class DGNLayerTower(nn.Module):
         rm, rv, nbt = self._linked_bn_stats(h.device)
         w_edge = graph.edge_weights(self._kplan_x, eig)
         mix = self.mixing_network.linear
-        drop = None
-        if self.dropout > 0:
-            seed, offset = _next_dropout_key(h.device)
-            drop = (float(self.dropout), seed, offset)
+        drop = _block_dropout(self, h)
         y = towers_layer(graph, self._kplan_x, self._avg_log, w_edge, h, snorm_n if self.graph_norm else None, sc, rm, rv, nbt,
                          ops["w_sd"], ops["bias_sd"], ops["w"], ops["b_p"], ops["bn_gamma"], ops["bn_beta"], mix.weight, mix.bias,
                          T, fi, fo, self.residual, bns[0].momentum, bns[0].eps, act[1], dropout=drop,
@@ -897,11 +855,6 @@ class DGNLayerTower(nn.Module):
         if drop is not None:
             _dropout_key_used(drop[1])
         return y
-
-    def forward(self, g, h, e, snorm_n):
-        # (a batch padded to a fixed row capacity carries its valid-row count as a device scalar: BatchNorm must know, ops.padded_rows)
-        with _ops.padded_rows(getattr(g, "n_valid", None)):
-            return self._forward(g, h, e, snorm_n)
 
     def _block_layer(self, g, h, snorm_n):
         """The layer on the graph-block route (ops.block_layer), or None: as _whole_layer's domain, per-tower parameters as they are."""
@@ -921,10 +874,7 @@ class DGNLayerTower(nn.Module):
             return None
         bns = [t.batchnorm_h for t in self.towers]
         rm, rv, nbt = self._linked_bn_stats(h.device)
-        drop = None
-        if self.dropout > 0 and self.training:      # the towers' F.dropout (:275) inside the route's tail kernels (round 6)
-            seed, offset = _next_dropout_key(h.device)
-            drop = (float(self.dropout), seed, offset)
+        drop = _block_dropout(self, h)      # the towers' F.dropout (:275) inside the route's tail kernels (round 6)
         y = _ops.block_layer(graph, self.plan, self._avg_log, g.ndata["eig"], h, snorm_n if self.graph_norm else None, rm, rv, nbt,
                              (*plist, mix.weight, mix.bias), 2, T, fi, fo, self.residual, bns[0].momentum, bns[0].eps, act[1], training=self.training,
                              dropout=drop)

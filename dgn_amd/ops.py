@@ -22,6 +22,14 @@ from .spec import EPS, AggPlan
 # sweep can use >= 8-byte lanes (even F: measured 8-14 % faster on the molecule configs), atomics otherwise (odd F,
 # e.g. hidden 75: 4-byte staging rows make the two-phase path 40 % slower than atomics).
 DETERMINISTIC_BACKWARD = "auto"
+
+
+def _two_phase_scatter(F: int) -> bool:
+    """The rule behind DETERMINISTIC_BACKWARD for a sweep of width F (see the switch): whether the backward scatter of d x_src runs
+    two-phase.  An edge-type table NEEDS it (launch_backward raises otherwise), so whoever hands one over asks here first."""
+    return (F % 2 == 0) if DETERMINISTIC_BACKWARD == "auto" else bool(DETERMINISTIC_BACKWARD)
+
+
 # Block backward (csrc/dgn_agg_block.hpp): on batches of small graphs (molecules) one wave owns whole graphs and accumulates d x_src in
 # its own LDS rows -- one kernel, no [E, F] staging round trip (1.2-1.7x the algorithmic traffic on the measured configs), the adds in
 # the staged path's own order (run-to-run reproducible).  True (default): used wherever the graph and the aggregator list have such a
@@ -181,8 +189,7 @@ def launch_backward(graph: DGNGraph, plan: AggPlan, n_towers: int, avg_log: floa
     specs = _spec_structs(plan, n_towers, avg_log, tower_stride)
     g = graph.c_graph
     first = True
-    deterministic = (F % 2 == 0) if DETERMINISTIC_BACKWARD == "auto" else bool(DETERMINISTIC_BACKWARD)
-    deterministic = deterministic and g_src is not None
+    deterministic = _two_phase_scatter(F) and g_src is not None
     if edge_type is not None and not deterministic:
         raise _lib.DgnError("edge-type table: the backward needs the two-phase scatter (even F, a gradient for x_src)")
     if deterministic:
@@ -335,39 +342,121 @@ def directional_aggregate(graph: DGNGraph, plan: AggPlan, avg_log, x_src: Option
                                        None if xin_is_src else x_in, xin_is_src, tower_major, None, edge_type)
 
 
+def _flat_operands(scale, bias, row_scale):
+    """The per-node / per-channel operands as the kernels read them: ``scale [N, S]`` dense, ``bias`` and ``row_scale`` (snorm_n [N, 1])
+    flat and dense; None stays None."""
+    return (None if scale is None else scale.contiguous(), None if bias is None else bias.reshape(-1).contiguous(),
+            None if row_scale is None else row_scale.reshape(-1).contiguous())
+
+
+def _kernel_counter(nbt, max_counters: int = 0):
+    """``num_batches_tracked`` of a training step: returned as it is when the statistics' finalize kernel can count it (ABI 28: CUDA
+    int64, dense, at most ``max_counters`` of them), else incremented here on the host and None returned (``max_counters`` 0: the entry
+    point has no counter argument)."""
+    if nbt is None or (nbt.is_cuda and nbt.dtype == torch.int64 and nbt.is_contiguous() and 1 <= nbt.numel() <= max_counters):
+        return nbt
+    with torch.no_grad():
+        nbt.add_(1)
+    return None
+
+
+# ---- launches of the tail kernels: what their callers have no reason to know (workspaces, save_* buffers, stream, return code) ----------
+
+def _combine_forward(z, scale, bias, row_scale):
+    """dgn_scale_combine_forward on ``z [T, N, S * fo]`` -> (y [N, T * fo], (T, N, S, fo))."""
+    lib = _lib.load()
+    T, N, W = z.shape
+    S = 1 if scale is None else scale.shape[1]
+    fo = W // S
+    z = z.contiguous()
+    y = torch.empty((N, T * fo), dtype=torch.float32, device=z.device)
+    rc = lib.dgn_scale_combine_forward(N, T, S, fo, z.data_ptr(), _ptr(scale), _ptr(bias), _ptr(row_scale), y.data_ptr(),
+                                       y.stride(0), _lib.stream_ptr(z.device))
+    _lib.check(rc, "dgn_scale_combine_forward")
+    return y, (T, N, S, fo)
+
+
+def _combine_backward(T, N, S, fo, scale, row_scale, want_bias, dev, g_y=None, bn=None):
+    """dgn_scale_combine_backward -> (g_z [T, N, S * fo], g_bias [T * fo] | None); the upstream gradient is ``g_y [N, T * fo]`` (dense)
+    or formed on the fly from a BatchNorm tail's inputs (``bn``: a DgnBnGrad, see _bn_combine_backward)."""
+    lib = _lib.load()
+    g_z = torch.empty((T, N, S * fo), dtype=torch.float32, device=dev)
+    g_b = torch.zeros(T * fo, dtype=torch.float32, device=dev) if want_bias else None
+    ws_bytes = lib.dgn_scale_combine_backward_workspace_bytes(N, T, fo) if g_b is not None else 0
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev) if ws_bytes else None
+    rc = lib.dgn_scale_combine_backward(N, T, S, fo, _ptr(g_y), g_y.stride(0) if g_y is not None else 0, _ptr(scale), _ptr(row_scale),
+                                        g_z.data_ptr(), _ptr(g_b), _ptr(ws), ws_bytes, C.byref(bn) if bn is not None else None,
+                                        _lib.stream_ptr(dev))
+    _lib.check(rc, "dgn_scale_combine_backward")
+    return g_z, g_b
+
+
+def _bn_forward(x, gamma, beta, running_mean, running_var, momentum, eps, training, relu, residual):
+    """dgn_bn_tail_forward on dense ``x [N, F]`` -> (y, save_mean, save_invstd, n_valid): ``n_valid`` is the padded batch's valid-row
+    count announced for this forward (padded_rows), which the node keeps for its backward."""
+    lib = _lib.load()
+    N, F = x.shape
+    dev = x.device
+    if residual is not None:
+        residual = residual.contiguous()
+    y = torch.empty_like(x)
+    save_mean = torch.empty(F, dtype=torch.float32, device=dev)
+    save_invstd = torch.empty(F, dtype=torch.float32, device=dev)
+    ws_bytes = lib.dgn_bn_tail_workspace_bytes(N, F) if training else 0      # (fp64 partial sums of the batch statistics)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev) if training else None
+    n_valid = _N_VALID
+    rc = lib.dgn_bn_tail_forward(N, F, x.data_ptr(), x.stride(0), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
+                                 float(momentum), float(eps), 1 if training else 0, 1 if relu else 0, _ptr(residual), y.data_ptr(),
+                                 save_mean.data_ptr(), save_invstd.data_ptr(), _ptr(ws), ws_bytes, _ptr(n_valid), _lib.stream_ptr(dev))
+    _lib.check(rc, "dgn_bn_tail_forward")
+    return y, save_mean, save_invstd, n_valid
+
+
+def _bn_backward(g_y, x, gamma, beta, save_mean, save_invstd, relu, n_valid, to_sums: bool):
+    """dgn_bn_tail_backward -> (sink, g_gamma, g_beta).  The sink is ``g_x [N, F]`` or, with ``to_sums``, the 2 F column sums alone: the
+    consumer of g_x then forms it on the fly from the tail's inputs (DgnBnGrad) and the [N, F] gradient is never written."""
+    lib = _lib.load()
+    N, F = x.shape
+    dev = x.device
+    sink = torch.empty(2 * F, dtype=torch.float32, device=dev) if to_sums else torch.empty_like(x)
+    g_gamma = torch.empty(F, dtype=torch.float32, device=dev) if gamma is not None else None
+    g_beta = torch.empty(F, dtype=torch.float32, device=dev) if beta is not None else None
+    ws_bytes = lib.dgn_bn_tail_workspace_bytes(N, F)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
+    rc = lib.dgn_bn_tail_backward(N, F, g_y.data_ptr(), x.data_ptr(), x.stride(0), _ptr(gamma), _ptr(beta), save_mean.data_ptr(),
+                                  save_invstd.data_ptr(), 1 if relu else 0, None if to_sums else sink.data_ptr(), _ptr(g_gamma), _ptr(g_beta),
+                                  sink.data_ptr() if to_sums else None, ws.data_ptr(), ws_bytes, _ptr(n_valid), _lib.stream_ptr(dev))
+    _lib.check(rc, "dgn_bn_tail_backward")
+    return sink, g_gamma, g_beta
+
+
+def _bn_combine_backward(g_out, y, gamma, beta, save_mean, save_invstd, relu, n_valid, T, N, S, fo, scale, row_scale, want_bias):
+    """Backward of a BatchNorm tail on ``y = scale_combine(...)`` -> (g_z, g_bias, g_gamma, g_beta): the tail's backward leaves its column
+    sums only, the combine's backward forms its upstream gradient from them and the tail's inputs."""
+    sums, g_gamma, g_beta = _bn_backward(g_out, y, gamma, beta, save_mean, save_invstd, relu, n_valid, to_sums=True)
+    bn = _lib.DgnBnGrad(g_out=g_out.data_ptr(), y=y.data_ptr(), ld=y.stride(0), gamma=_ptr(gamma), beta=_ptr(beta),
+                        mean=save_mean.data_ptr(), invstd=save_invstd.data_ptr(), sums=sums.data_ptr(), relu=1 if relu else 0,
+                        n_valid=_ptr(n_valid))
+    g_z, g_b = _combine_backward(T, N, S, fo, scale, row_scale, want_bias, y.device, bn=bn)
+    return g_z, g_b, g_gamma, g_beta
+
+
 class _ScaleCombine(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, scale, bias, row_scale):
-        lib = _lib.load()
         if not z.is_cuda:
             raise _lib.DgnError("scale_combine: CUDA tensors only (dgn_amd has no CPU path)")
-        T, N, W = z.shape
-        S = 1 if scale is None else scale.shape[1]
-        fo = W // S
-        z = z.contiguous()
-        y = torch.empty((N, T * fo), dtype=torch.float32, device=z.device)
-        stream = _lib.stream_ptr(z.device)
-        rc = lib.dgn_scale_combine_forward(N, T, S, fo, z.data_ptr(), _ptr(scale), _ptr(bias), _ptr(row_scale), y.data_ptr(),
-                                           y.stride(0), stream)
-        _lib.check(rc, "dgn_scale_combine_forward")
+        y, dims = _combine_forward(z, scale, bias, row_scale)
         ctx.save_for_backward(scale, row_scale)
-        ctx.dims = (T, N, S, fo, bias is not None)
+        ctx.dims = dims + (bias is not None,)
         return y
 
     @staticmethod
     def backward(ctx, g_y):
-        lib = _lib.load()
         scale, row_scale = ctx.saved_tensors
         T, N, S, fo, has_bias = ctx.dims
         g_y = g_y.contiguous()
-        g_z = torch.empty((T, N, S * fo), dtype=torch.float32, device=g_y.device)
-        g_b = torch.zeros(T * fo, dtype=torch.float32, device=g_y.device) if (has_bias and ctx.needs_input_grad[2]) else None
-        ws_bytes = lib.dgn_scale_combine_backward_workspace_bytes(N, T, fo) if g_b is not None else 0
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=g_y.device) if ws_bytes else None
-        stream = _lib.stream_ptr(g_y.device)
-        rc = lib.dgn_scale_combine_backward(N, T, S, fo, g_y.data_ptr(), g_y.stride(0), _ptr(scale), _ptr(row_scale),
-                                            g_z.data_ptr(), _ptr(g_b), _ptr(ws), ws_bytes, None, stream)
-        _lib.check(rc, "dgn_scale_combine_backward")
+        g_z, g_b = _combine_backward(T, N, S, fo, scale, row_scale, has_bias and ctx.needs_input_grad[2], g_y.device, g_y=g_y)
         return g_z, None, g_b, None
 
 
@@ -378,13 +467,7 @@ def scale_combine(z: torch.Tensor, scale: Optional[torch.Tensor], bias: Optional
     ``z [T, N, S*fo]`` is the output of the (batched) post-aggregation GEMM on the scaler-free sweep output,
     ``scale [N, S]`` the degree-scaler table (None: single identity), ``row_scale [N]`` the graph-norm factor
     snorm_n (None: no graph norm).  One streaming kernel instead of mul + sum + add + mul + re-layout."""
-    if scale is not None:
-        scale = scale.contiguous()
-    if row_scale is not None:
-        row_scale = row_scale.reshape(-1).contiguous()
-    if bias is not None:
-        bias = bias.reshape(-1).contiguous()
-    return _ScaleCombine.apply(z, scale, bias, row_scale)
+    return _ScaleCombine.apply(z, *_flat_operands(scale, bias, row_scale))
 
 
 class _Dropout(torch.autograd.Function):
@@ -437,44 +520,19 @@ def dropout(x: torch.Tensor, p: float, training: bool, seed: Optional[torch.Tens
 class _BNTail(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, training, relu, residual):
-        lib = _lib.load()
         if not x.is_cuda:
             raise _lib.DgnError("bn_tail: CUDA tensors only (dgn_amd has no CPU path)")
         x = x.contiguous()
-        N, F = x.shape
-        if residual is not None:
-            residual = residual.contiguous()
-        y = torch.empty_like(x)
-        save_mean = torch.empty(F, dtype=torch.float32, device=x.device)
-        save_invstd = torch.empty(F, dtype=torch.float32, device=x.device)
-        ws_bytes = lib.dgn_bn_tail_workspace_bytes(N, F) if training else 0
-        ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=x.device) if ws_bytes else None
-        stream = _lib.stream_ptr(x.device)
-        ctx.n_valid = _N_VALID
-        rc = lib.dgn_bn_tail_forward(N, F, x.data_ptr(), x.stride(0), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
-                                     float(momentum), float(eps), 1 if training else 0, 1 if relu else 0, _ptr(residual), y.data_ptr(),
-                                     save_mean.data_ptr(), save_invstd.data_ptr(), _ptr(ws), ws_bytes, _ptr(ctx.n_valid), stream)
-        _lib.check(rc, "dgn_bn_tail_forward")
+        y, save_mean, save_invstd, ctx.n_valid = _bn_forward(x, gamma, beta, running_mean, running_var, momentum, eps, training, relu, residual)
         ctx.save_for_backward(x, gamma, beta, save_mean, save_invstd)
         ctx.relu, ctx.has_res = relu, residual is not None
         return y
 
     @staticmethod
     def backward(ctx, g_y):
-        lib = _lib.load()
         x, gamma, beta, save_mean, save_invstd = ctx.saved_tensors
         g_y = g_y.contiguous()
-        N, F = x.shape
-        g_x = torch.empty_like(x)
-        g_gamma = torch.empty(F, dtype=torch.float32, device=x.device) if gamma is not None else None
-        g_beta = torch.empty(F, dtype=torch.float32, device=x.device) if beta is not None else None
-        ws_bytes = lib.dgn_bn_tail_workspace_bytes(N, F)
-        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=x.device)
-        stream = _lib.stream_ptr(x.device)
-        rc = lib.dgn_bn_tail_backward(N, F, g_y.data_ptr(), x.data_ptr(), x.stride(0), _ptr(gamma), _ptr(beta), save_mean.data_ptr(),
-                                      save_invstd.data_ptr(), 1 if ctx.relu else 0, g_x.data_ptr(), _ptr(g_gamma), _ptr(g_beta),
-                                      None, ws.data_ptr(), ws_bytes, _ptr(ctx.n_valid), stream)
-        _lib.check(rc, "dgn_bn_tail_backward")
+        g_x, g_gamma, g_beta = _bn_backward(g_y, x, gamma, beta, save_mean, save_invstd, ctx.relu, ctx.n_valid, to_sums=False)
         return g_x, g_gamma, g_beta, None, None, None, None, None, None, (g_y if ctx.has_res else None)
 
 
@@ -485,63 +543,21 @@ class _CombineBNTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, scale, bias, row_scale, gamma, beta, running_mean, running_var, momentum, eps, relu, residual):
-        lib = _lib.load()
         if not z.is_cuda:
             raise _lib.DgnError("combine_bn_tail: CUDA tensors only (dgn_amd has no CPU path)")
-        T, N, W = z.shape
-        S = 1 if scale is None else scale.shape[1]
-        fo = W // S
-        F = T * fo
-        z = z.contiguous()
-        dev = z.device
-        stream = _lib.stream_ptr(dev)
-        y = torch.empty((N, F), dtype=torch.float32, device=dev)
-        rc = lib.dgn_scale_combine_forward(N, T, S, fo, z.data_ptr(), _ptr(scale), _ptr(bias), _ptr(row_scale), y.data_ptr(), y.stride(0), stream)
-        _lib.check(rc, "dgn_scale_combine_forward")
-        if residual is not None:
-            residual = residual.contiguous()
-        out = torch.empty_like(y)
-        save_mean = torch.empty(F, dtype=torch.float32, device=dev)
-        save_invstd = torch.empty(F, dtype=torch.float32, device=dev)
-        ws_bytes = lib.dgn_bn_tail_workspace_bytes(N, F)
-        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
-        ctx.n_valid = _N_VALID
-        rc = lib.dgn_bn_tail_forward(N, F, y.data_ptr(), y.stride(0), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
-                                     float(momentum), float(eps), 1, 1 if relu else 0, _ptr(residual), out.data_ptr(),
-                                     save_mean.data_ptr(), save_invstd.data_ptr(), ws.data_ptr(), ws_bytes, _ptr(ctx.n_valid), stream)
-        _lib.check(rc, "dgn_bn_tail_forward")
+        y, dims = _combine_forward(z, scale, bias, row_scale)
+        out, save_mean, save_invstd, ctx.n_valid = _bn_forward(y, gamma, beta, running_mean, running_var, momentum, eps, True, relu, residual)
         ctx.save_for_backward(scale, row_scale, y, gamma, beta, save_mean, save_invstd)
-        ctx.dims = (T, N, S, fo, bias is not None, relu, residual is not None)
+        ctx.dims = dims + (bias is not None, relu, residual is not None)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = _lib.load()
         scale, row_scale, y, gamma, beta, save_mean, save_invstd = ctx.saved_tensors
         T, N, S, fo, has_bias, relu, has_res = ctx.dims
-        F = T * fo
-        dev = y.device
         g_out = g_out.contiguous()
-        stream = _lib.stream_ptr(dev)
-        g_gamma = torch.empty(F, dtype=torch.float32, device=dev) if gamma is not None else None
-        g_beta = torch.empty(F, dtype=torch.float32, device=dev) if beta is not None else None
-        sums = torch.empty(2 * F, dtype=torch.float32, device=dev)
-        ws_bytes = lib.dgn_bn_tail_workspace_bytes(N, F)
-        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
-        rc = lib.dgn_bn_tail_backward(N, F, g_out.data_ptr(), y.data_ptr(), y.stride(0), _ptr(gamma), _ptr(beta), save_mean.data_ptr(),
-                                      save_invstd.data_ptr(), 1 if relu else 0, None, _ptr(g_gamma), _ptr(g_beta), sums.data_ptr(),
-                                      ws.data_ptr(), ws_bytes, _ptr(ctx.n_valid), stream)
-        _lib.check(rc, "dgn_bn_tail_backward")
-        bn = _lib.DgnBnGrad(g_out=g_out.data_ptr(), y=y.data_ptr(), ld=y.stride(0), gamma=_ptr(gamma), beta=_ptr(beta),
-                            mean=save_mean.data_ptr(), invstd=save_invstd.data_ptr(), sums=sums.data_ptr(), relu=1 if relu else 0,
-                            n_valid=_ptr(ctx.n_valid))
-        g_z = torch.empty((T, N, S * fo), dtype=torch.float32, device=dev)
-        g_b = torch.zeros(F, dtype=torch.float32, device=dev) if (has_bias and ctx.needs_input_grad[2]) else None
-        ws2_bytes = lib.dgn_scale_combine_backward_workspace_bytes(N, T, fo) if g_b is not None else 0
-        ws2 = torch.empty(ws2_bytes // 4, dtype=torch.float32, device=dev) if ws2_bytes else None
-        rc = lib.dgn_scale_combine_backward(N, T, S, fo, None, 0, _ptr(scale), _ptr(row_scale), g_z.data_ptr(), _ptr(g_b), _ptr(ws2),
-                                            ws2_bytes, C.byref(bn), stream)
-        _lib.check(rc, "dgn_scale_combine_backward")
+        g_z, g_b, g_gamma, g_beta = _bn_combine_backward(g_out, y, gamma, beta, save_mean, save_invstd, relu, ctx.n_valid, T, N, S, fo, scale,
+                                                         row_scale, has_bias and ctx.needs_input_grad[2])
         return g_z, None, g_b, None, g_gamma, g_beta, None, None, None, None, None, (g_out if has_res else None)
 
 
@@ -549,16 +565,9 @@ def combine_bn_tail(z, scale, bias, row_scale, gamma, beta, running_mean, runnin
                     relu: bool = False, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``[relu](BatchNorm(scale_combine(z, scale, bias, row_scale))) [+ residual]`` in TRAINING mode as one autograd node
     (see _CombineBNTail); running statistics are updated in place.  Needs n_towers * f_out <= 1024."""
-    if scale is not None:
-        scale = scale.contiguous()
-    if row_scale is not None:
-        row_scale = row_scale.reshape(-1).contiguous()
-    if bias is not None:
-        bias = bias.reshape(-1).contiguous()
+    scale, bias, row_scale = _flat_operands(scale, bias, row_scale)
     out = _CombineBNTail.apply(z, scale, bias, row_scale, gamma, beta, running_mean, running_var, momentum, eps, relu, residual)
-    if num_batches_tracked is not None:
-        with torch.no_grad():
-            num_batches_tracked.add_(1)
+    _kernel_counter(num_batches_tracked)
     return out
 
 
@@ -617,9 +626,8 @@ def bn_tail_fused(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, runn
     fused operand buffer and its running statistics in one tensor the per-tower modules view): no cat before and no
     scatter after the kernels.  Running statistics are updated in place."""
     y = _BNTail.apply(x, gamma, beta, running_mean, running_var, momentum, eps, training, relu, residual)
-    if training and num_batches_tracked is not None:
-        with torch.no_grad():
-            num_batches_tracked.add_(1)
+    if training:
+        _kernel_counter(num_batches_tracked)
     return y
 
 
@@ -628,10 +636,15 @@ def _spans_ranks(bn, training: bool) -> bool:
     return training and getattr(bn, "dgn_sync", False) and torch.distributed.is_available() and torch.distributed.is_initialized()
 
 
+def _bn_fusable(bn, training: bool) -> bool:
+    """The BatchNorm module's share of "the fused tail applies": affine, running statistics with a momentum, statistics of the local rows."""
+    return bn.affine and bn.track_running_stats and bn.momentum is not None and not _spans_ranks(bn, training)
+
+
 def bn_tail_supported(bns, x: torch.Tensor, training: bool, width: Optional[int] = None) -> bool:
     """What the fused tail kernels cover: affine BatchNorm with running statistics, F <= 1024 (``width``, default
     ``x.shape[1]``), and -- with gradients -- training mode."""
-    simple = all(b.affine and b.track_running_stats and b.momentum is not None and not _spans_ranks(b, training) for b in bns)
+    simple = all(_bn_fusable(b, training) for b in bns)
     needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for b in bns for p in b.parameters()))
     return simple and (x.shape[1] if width is None else width) <= 1024 and (training or not needs_grad)
 
@@ -645,9 +658,7 @@ def bn_tail(x: torch.Tensor, bns, training: bool, relu: bool = False, residual: 
     if not isinstance(bns, (list, tuple)):
         bns = [bns]
     b0 = bns[0]
-    simple = all(b.affine and b.track_running_stats and b.momentum is not None and not _spans_ranks(b, training) for b in bns)
-    needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for b in bns for p in b.parameters()))
-    if not simple or x.shape[1] > 1024 or (not training and needs_grad):   # (fused: training-mode backward, F <= 1024)
+    if not bn_tail_supported(bns, x, training):   # (fused: training-mode backward, F <= 1024)
         # configurations the fused kernels do not cover: plain torch modules
         if _N_VALID is not None and training:
             raise _lib.DgnError("padded batch (n_valid): this BatchNorm configuration runs on plain torch modules, which would count the "
@@ -933,25 +944,12 @@ class _LinCombineBNTail(torch.autograd.Function):
         T, N, k = aggx.shape
         S = 1 if scale is None else scale.shape[1]
         fo = w.shape[1] // S
-        F = T * fo
         dev = aggx.device
-        stream = _lib.stream_ptr(dev)
-        y = torch.empty((N, F), dtype=torch.float32, device=dev)
+        y = torch.empty((N, T * fo), dtype=torch.float32, device=dev)
         rc = lib.dgn_linear_combine_forward(N, k, T, S, fo, aggx.data_ptr(), aggx.stride(0), w.data_ptr(), w.stride(1), w.stride(0),
-                                            _ptr(scale), _ptr(bias), _ptr(row_scale), y.data_ptr(), y.stride(0), stream)
+                                            _ptr(scale), _ptr(bias), _ptr(row_scale), y.data_ptr(), y.stride(0), _lib.stream_ptr(dev))
         _lib.check(rc, "dgn_linear_combine_forward")
-        if residual is not None:
-            residual = residual.contiguous()
-        out = torch.empty_like(y)
-        save_mean = torch.empty(F, dtype=torch.float32, device=dev)
-        save_invstd = torch.empty(F, dtype=torch.float32, device=dev)
-        ws_bytes = lib.dgn_bn_tail_workspace_bytes(N, F)
-        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
-        ctx.n_valid = _N_VALID
-        rc = lib.dgn_bn_tail_forward(N, F, y.data_ptr(), y.stride(0), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
-                                     float(momentum), float(eps), 1, 1 if relu else 0, _ptr(residual), out.data_ptr(),
-                                     save_mean.data_ptr(), save_invstd.data_ptr(), ws.data_ptr(), ws_bytes, _ptr(ctx.n_valid), stream)
-        _lib.check(rc, "dgn_bn_tail_forward")
+        out, save_mean, save_invstd, ctx.n_valid = _bn_forward(y, gamma, beta, running_mean, running_var, momentum, eps, True, relu, residual)
         ctx.save_for_backward(scale, row_scale, y, gamma, beta, save_mean, save_invstd, aggx, w)
         ctx.dims = (T, N, S, fo, bias is not None, relu, residual is not None)
         return out
@@ -961,31 +959,14 @@ class _LinCombineBNTail(torch.autograd.Function):
         lib = _lib.load()
         scale, row_scale, y, gamma, beta, save_mean, save_invstd, aggx, w = ctx.saved_tensors
         T, N, S, fo, has_bias, relu, has_res = ctx.dims
-        F, k = T * fo, aggx.shape[2]
+        k = aggx.shape[2]
         dev = y.device
         g_out = g_out.contiguous()
         stream = _lib.stream_ptr(dev)
-        g_gamma = torch.empty(F, dtype=torch.float32, device=dev) if gamma is not None else None
-        g_beta = torch.empty(F, dtype=torch.float32, device=dev) if beta is not None else None
-        sums = torch.empty(2 * F, dtype=torch.float32, device=dev)
-        ws_bytes = lib.dgn_bn_tail_workspace_bytes(N, F)
-        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
-        rc = lib.dgn_bn_tail_backward(N, F, g_out.data_ptr(), y.data_ptr(), y.stride(0), _ptr(gamma), _ptr(beta), save_mean.data_ptr(),
-                                      save_invstd.data_ptr(), 1 if relu else 0, None, _ptr(g_gamma), _ptr(g_beta), sums.data_ptr(),
-                                      ws.data_ptr(), ws_bytes, _ptr(ctx.n_valid), stream)
-        _lib.check(rc, "dgn_bn_tail_backward")
-        bn = _lib.DgnBnGrad(g_out=g_out.data_ptr(), y=y.data_ptr(), ld=y.stride(0), gamma=_ptr(gamma), beta=_ptr(beta),
-                            mean=save_mean.data_ptr(), invstd=save_invstd.data_ptr(), sums=sums.data_ptr(), relu=1 if relu else 0,
-                            n_valid=_ptr(ctx.n_valid))
         # g_yr = row_scale * (BatchNorm backward of g_out), tower-major [T, N, fo]: the combine backward run with ONE scaler and
         # no scale table; the per-scaler expansion happens inside the two products below
-        g_yr = torch.empty((T, N, fo), dtype=torch.float32, device=dev)
-        g_b = torch.zeros(F, dtype=torch.float32, device=dev) if (has_bias and ctx.needs_input_grad[3]) else None
-        ws2_bytes = lib.dgn_scale_combine_backward_workspace_bytes(N, T, fo) if g_b is not None else 0
-        ws2 = torch.empty(ws2_bytes // 4, dtype=torch.float32, device=dev) if ws2_bytes else None
-        rc = lib.dgn_scale_combine_backward(N, T, 1, fo, None, 0, None, _ptr(row_scale), g_yr.data_ptr(), _ptr(g_b), _ptr(ws2),
-                                            ws2_bytes, C.byref(bn), stream)
-        _lib.check(rc, "dgn_scale_combine_backward")
+        g_yr, g_b, g_gamma, g_beta = _bn_combine_backward(g_out, y, gamma, beta, save_mean, save_invstd, relu, ctx.n_valid, T, N, 1, fo, None,
+                                                          row_scale, has_bias and ctx.needs_input_grad[3])
         g_aggx = g_w = None
         if ctx.needs_input_grad[0]:
             g_aggx = torch.empty_like(aggx)
@@ -1013,16 +994,9 @@ def linear_combine_bn_tail(aggx, w, scale, bias, row_scale, gamma, beta, running
     """``[relu](BatchNorm(scale_combine(bmm(aggx, w^T), scale, bias, row_scale))) [+ residual]`` in TRAINING mode as one
     autograd node; ``aggx [T, N, k]`` (the sweep's tower-major output), ``w [T, S*fo, k]``.  Running statistics are
     updated in place.  Needs ``linear_supported(k, S*fo)`` and ``T*fo <= 1024``."""
-    if scale is not None:
-        scale = scale.contiguous()
-    if row_scale is not None:
-        row_scale = row_scale.reshape(-1).contiguous()
-    if bias is not None:
-        bias = bias.reshape(-1).contiguous()
+    scale, bias, row_scale = _flat_operands(scale, bias, row_scale)
     out = _LinCombineBNTail.apply(aggx, w, scale, bias, row_scale, gamma, beta, running_mean, running_var, momentum, eps, relu, residual)
-    if num_batches_tracked is not None:
-        with torch.no_grad():
-            num_batches_tracked.add_(1)
+    _kernel_counter(num_batches_tracked)
     return out
 
 
@@ -1045,26 +1019,76 @@ def towers_layer_supported(n_towers: int, f_in: int, f_out: int, n_scalers: int,
     return _TOWERS_OK[key]
 
 
-def _carve(sizes, device):
-    """one allocation, views of the given element counts (each view starts 256-byte aligned)"""
+def _up64(n: int) -> int:
+    """element count rounded up to 256 bytes of fp32"""
+    return (n + 63) & ~63
+
+
+def _carve_offsets(sizes):
+    """(start of each view, total) in elements: every view starts 256-byte aligned"""
     offs, total = [], 0
     for n in sizes:
         offs.append(total)
-        total += (n + 63) & ~63
-    buf = torch.empty(max(total, 1), dtype=torch.float32, device=device)
+        total += _up64(n)
+    return offs, total
+
+
+def _carve(sizes, device, buf=None):
+    """one allocation (or ``buf``, an earlier call's), views of the given element counts"""
+    offs, total = _carve_offsets(sizes)
+    if buf is None:
+        buf = torch.empty(max(total, 1), dtype=torch.float32, device=device)
     return buf, [buf[o:o + n] for o, n in zip(offs, sizes)]
 
 
 def _carve_ptrs(sizes, device, buf=None):
     """_carve for callers that only pass addresses on: (buffer, [address or None per view]) -- no view tensors are created"""
-    offs, total = [], 0
-    for n in sizes:
-        offs.append(total)
-        total += (n + 63) & ~63
+    offs, total = _carve_offsets(sizes)
     if buf is None:
         buf = torch.empty(max(total, 1), dtype=torch.float32, device=device)
     base = buf.data_ptr()
     return buf, [base + 4 * o if n else None for o, n in zip(offs, sizes)]
+
+
+def _layer_workspace(L, nbytes, dev):
+    """the scratch of a whole-layer call: allocated, named in the struct, returned to be kept until the call is enqueued"""
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    L.ws, L.ws_bytes = ws.data_ptr(), nbytes
+    return ws
+
+
+def _towers_saved_sizes(cfg, plan, N, n_y1, n_z):
+    """Element counts of what the towers layer's forward leaves for its backward, in the order of one _carve'd buffer:
+    pq, aggx, y0, y1 (0: not materialised), z (or its byte mask), save_mean, save_invstd."""
+    T, fi, fo = cfg[:3]
+    return [N * 2 * T * fi, T * N * plan.n_agg * fi, N * T * fo, n_y1, n_z, T * fo, T * fo]
+
+
+def _towers_struct(graph, plan, avg_log, w_edge, cfg, h, snorm, scale, w_sd, bias_sd, w_post, b_post, gamma, beta, w_mix, b_mix, bufs, use_mask,
+                   aux, drop_mask, n_valid):
+    """DgnTowersLayer as both directions read it (+ the ctypes objects it points to); the forward adds the running statistics, the
+    counters, ``out`` and the dropout key, the backward ``id_slot1``."""
+    T, fi, fo, S, residual, momentum, eps, slope, drop = cfg[:9]
+    pq, aggx, y0, y1, z, mean, invstd = bufs
+    spec = _spec_structs(plan, T, avg_log, h.shape[0] * plan.n_agg * fi)[0]
+    L = _lib.DgnTowersLayer()
+    cg = graph.c_graph
+    L.graph, L.spec = C.pointer(cg), C.pointer(spec)
+    L.w, L.ld_w, L.log_deg = _ptr(w_edge), (w_edge.stride(0) if w_edge is not None else 0), graph.log_deg.data_ptr()
+    L.n_towers, L.f_in, L.f_out, L.n_scalers, L.residual = T, fi, fo, S, int(residual)
+    L.momentum, L.eps, L.slope = float(momentum), float(eps), float(slope)
+    L.h, L.snorm, L.scale = h.data_ptr(), _ptr(snorm), _ptr(scale)
+    L.w_sd, L.bias_sd, L.w_post, L.b_post = w_sd.data_ptr(), bias_sd.data_ptr(), w_post.data_ptr(), b_post.data_ptr()
+    L.bn_gamma, L.bn_beta = gamma.data_ptr(), beta.data_ptr()
+    L.w_mix, L.b_mix = w_mix.data_ptr(), b_mix.data_ptr()
+    L.pq, L.aggx, L.y0, L.y1 = pq.data_ptr(), aggx.data_ptr(), y0.data_ptr(), (y1.data_ptr() if y1.numel() else None)
+    L.z, L.zmask = (None, z.data_ptr()) if use_mask else (z.data_ptr(), None)
+    L.save_mean, L.save_invstd = mean.data_ptr(), invstd.data_ptr()
+    L.agg_aux = _ptr(aux)
+    if drop is not None:
+        L.drop_p, L.drop_mask = drop[0], drop_mask.data_ptr()
+    L.n_valid = _ptr(n_valid)
+    return L, (cg, spec)
 
 
 class _TowersLayer(torch.autograd.Function):
@@ -1076,8 +1100,7 @@ class _TowersLayer(torch.autograd.Function):
         T, fi, fo, S, residual, momentum, eps, slope, drop = cfg[:9]
         if not h.is_cuda:
             raise _lib.DgnError("towers_layer: CUDA tensors only (dgn_amd has no CPU path)")
-        N, Fm, Fo = h.shape[0], T * fi, T * fo
-        K = plan.n_agg * fi
+        N, Fo = h.shape[0], T * fo
         dev = h.device
         h, w_sd, bias_sd, w_post, b_post = h.contiguous(), w_sd.contiguous(), bias_sd.contiguous(), w_post.contiguous(), b_post.contiguous()
         gamma, beta, w_mix, b_mix = gamma.contiguous(), beta.contiguous(), w_mix.contiguous(), b_mix.contiguous()
@@ -1089,41 +1112,25 @@ class _TowersLayer(torch.autograd.Function):
         # mask (DgnTowersLayer.zmask, 1/8 of the bytes) in the slot z would take
         use_mask = n_y1 == 0 and (h.data_ptr() & 15) == 0 and bool(lib.dgn_towers_layer_zmask_supported(T, fo))
         n_z = (lib.dgn_linear_act_mask_bytes(N, Fo) + 3) // 4 if use_mask else N * Fo
-        saved_buf, (pq, aggx, y0, y1, z, mean, invstd) = _carve([N * 2 * Fm, T * N * K, N * Fo, n_y1, n_z, Fo, Fo], dev)
+        saved_buf, bufs = _carve(_towers_saved_sizes(cfg, plan, N, n_y1, n_z), dev)
         ctx.n_y1, ctx.n_z, ctx.use_mask = n_y1, n_z, use_mask
         out = torch.empty((N, Fo), dtype=torch.float32, device=dev)
-        spec = _spec_structs(plan, T, avg_log, N * K)[0]
-        L = _lib.DgnTowersLayer()
-        cg = graph.c_graph
-        L.graph, L.spec = C.pointer(cg), C.pointer(spec)
-        L.w, L.ld_w, L.log_deg = _ptr(w_edge), (w_edge.stride(0) if w_edge is not None else 0), graph.log_deg.data_ptr()
-        L.n_towers, L.f_in, L.f_out, L.n_scalers, L.residual = T, fi, fo, S, int(residual)
-        L.momentum, L.eps, L.slope = float(momentum), float(eps), float(slope)
-        L.h, L.snorm, L.scale = h.data_ptr(), _ptr(snorm), _ptr(scale)
-        L.w_sd, L.bias_sd, L.w_post, L.b_post = w_sd.data_ptr(), bias_sd.data_ptr(), w_post.data_ptr(), b_post.data_ptr()
-        L.bn_gamma, L.bn_beta, L.running_mean, L.running_var = gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(), running_var.data_ptr()
-        L.w_mix, L.b_mix = w_mix.data_ptr(), b_mix.data_ptr()
-        L.pq, L.aggx, L.y0, L.y1 = pq.data_ptr(), aggx.data_ptr(), y0.data_ptr(), (y1.data_ptr() if n_y1 else None)
-        L.z, L.zmask = (None, z.data_ptr()) if use_mask else (z.data_ptr(), None)
-        L.save_mean, L.save_invstd, L.out = mean.data_ptr(), invstd.data_ptr(), out.data_ptr()
+        drop_mask = torch.empty(lib.dgn_dropout_mask_bytes(N * Fo), dtype=torch.uint8, device=dev) if drop is not None else None
+        ctx.n_valid = _N_VALID
+        L, keep = _towers_struct(graph, plan, avg_log, w_edge, cfg, h, snorm, scale, w_sd, bias_sd, w_post, b_post, gamma, beta, w_mix, b_mix, bufs,
+                                 use_mask, None, drop_mask, ctx.n_valid)
+        L.running_mean, L.running_var, L.out = running_mean.data_ptr(), running_var.data_ptr(), out.data_ptr()
         if nbt is not None:                              # (the counters ride in the statistics' finalize kernel: ABI 28)
             L.num_batches_tracked, L.n_nbt = nbt.data_ptr(), nbt.numel()
-        drop_mask = None
         if drop is not None:
-            drop_mask = torch.empty(lib.dgn_dropout_mask_bytes(N * Fo), dtype=torch.uint8, device=dev)
-            L.drop_p, L.drop_seed, L.drop_offset, L.drop_mask = drop[0], drop[1].data_ptr(), int(drop[2]), drop_mask.data_ptr()
+            L.drop_seed, L.drop_offset = drop[1].data_ptr(), int(drop[2])
             LAST_DROPOUT_MASK = drop_mask
         # what the backward sweep would recompute from the messages (first max / min slot, dx signs): one byte per (row, feature)
         n_aux = int(lib.dgn_towers_layer_agg_aux_bytes(C.byref(L))) if AGG_AUX else 0
         aux = torch.empty(n_aux, dtype=torch.uint8, device=dev) if n_aux else None
         L.agg_aux = _ptr(aux)
-        nbytes = lib.dgn_towers_layer_forward_workspace_bytes(C.byref(L))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        L.ws, L.ws_bytes = ws.data_ptr(), nbytes
-        ctx.n_valid = _N_VALID
-        L.n_valid = _ptr(ctx.n_valid)
-        stream = _lib.stream_ptr(dev)
-        _lib.check(lib.dgn_towers_layer_forward(C.byref(L), stream), "dgn_towers_layer_forward")
+        ws = _layer_workspace(L, lib.dgn_towers_layer_forward_workspace_bytes(C.byref(L)), dev)
+        _lib.check(lib.dgn_towers_layer_forward(C.byref(L), _lib.stream_ptr(dev)), "dgn_towers_layer_forward")
         ctx.save_for_backward(w_edge, h, snorm, scale, w_sd, bias_sd, w_post, b_post, gamma, beta, w_mix, b_mix, saved_buf, aux, drop_mask)
         ctx.graph, ctx.plan, ctx.avg_log, ctx.cfg = graph, plan, avg_log, cfg
         return out
@@ -1132,56 +1139,32 @@ class _TowersLayer(torch.autograd.Function):
     def backward(ctx, g_out):
         lib = _lib.load()
         w_edge, h, snorm, scale, w_sd, bias_sd, w_post, b_post, gamma, beta, w_mix, b_mix, saved_buf, aux, drop_mask = ctx.saved_tensors
-        graph, plan = ctx.graph, ctx.plan
-        T, fi, fo, S, residual, momentum, eps, slope, drop = ctx.cfg[:9]
-        id_slot = ctx.cfg[9] if len(ctx.cfg) > 9 else None
+        graph, plan, cfg = ctx.graph, ctx.plan, ctx.cfg
+        T, fi, fo, S = cfg[:4]
+        id_slot = cfg[9] if len(cfg) > 9 else None
         N, Fm, Fo = h.shape[0], T * fi, T * fo
         K = plan.n_agg * fi
         dev = h.device
-        sizes = [N * 2 * Fm, T * N * K, N * Fo, ctx.n_y1, ctx.n_z, Fo, Fo]
-        offs, total = [], 0
-        for n in sizes:
-            offs.append(total)
-            total += (n + 63) & ~63
-        pq, aggx, y0, y1, z, mean, invstd = (saved_buf[o:o + n] for o, n in zip(offs, sizes))
+        _, bufs = _carve(_towers_saved_sizes(cfg, plan, N, ctx.n_y1, ctx.n_z), dev, saved_buf)
         g_out = g_out.contiguous()
         graph.ensure_csc()
         graph.ensure_blocks(bool(BLOCK_BACKWARD))
-        spec = _spec_structs(plan, T, ctx.avg_log, N * K)[0]
-        L = _lib.DgnTowersLayer()
-        cg = graph.c_graph
-        L.graph, L.spec = C.pointer(cg), C.pointer(spec)
-        L.w, L.ld_w, L.log_deg = _ptr(w_edge), (w_edge.stride(0) if w_edge is not None else 0), graph.log_deg.data_ptr()
-        L.n_towers, L.f_in, L.f_out, L.n_scalers, L.residual = T, fi, fo, S, int(residual)
-        L.momentum, L.eps, L.slope = float(momentum), float(eps), float(slope)
-        L.h, L.snorm, L.scale = h.data_ptr(), _ptr(snorm), _ptr(scale)
-        L.w_sd, L.bias_sd, L.w_post, L.b_post = w_sd.data_ptr(), bias_sd.data_ptr(), w_post.data_ptr(), b_post.data_ptr()
-        L.bn_gamma, L.bn_beta = gamma.data_ptr(), beta.data_ptr()
-        L.w_mix, L.b_mix = w_mix.data_ptr(), b_mix.data_ptr()
-        L.pq, L.aggx, L.y0, L.y1 = pq.data_ptr(), aggx.data_ptr(), y0.data_ptr(), (y1.data_ptr() if ctx.n_y1 else None)
-        L.z, L.zmask = (None, z.data_ptr()) if ctx.use_mask else (z.data_ptr(), None)
-        L.save_mean, L.save_invstd = mean.data_ptr(), invstd.data_ptr()
-        L.agg_aux = _ptr(aux)
+        L, keep = _towers_struct(graph, plan, ctx.avg_log, w_edge, cfg, h, snorm, scale, w_sd, bias_sd, w_post, b_post, gamma, beta, w_mix, b_mix, bufs,
+                                 ctx.use_mask, aux, drop_mask, ctx.n_valid)
         L.id_slot1 = 0 if id_slot is None else int(id_slot) + 1
-        if drop is not None:
-            L.drop_p, L.drop_mask = drop[0], drop_mask.data_ptr()
-        nbytes = lib.dgn_towers_layer_backward_workspace_bytes(C.byref(L))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        L.ws, L.ws_bytes = ws.data_ptr(), nbytes
-        L.n_valid = _ptr(ctx.n_valid)
+        ws = _layer_workspace(L, lib.dgn_towers_layer_backward_workspace_bytes(C.byref(L)), dev)
         g_h = torch.empty((N, Fm), dtype=torch.float32, device=dev)
         # the six operand gradients back to back (no padding) in the order of DGNLayerTower._assemble's flat operand buffer: _AssembleOperands.backward
         # finds them adjacent and gathers the parameter gradients out of this buffer without a concatenation
         n_ops = [2 * Fm * Fm, 2 * Fm, Fo, Fo, Fo, T * S * fo * K]
-        n_flat = (sum(n_ops) + 63) & ~63
-        gbuf = torch.empty(n_flat + ((Fo * Fo + 63) & ~63) + Fo, dtype=torch.float32, device=dev)
+        n_flat = _up64(sum(n_ops))
+        gbuf = torch.empty(n_flat + _up64(Fo * Fo) + Fo, dtype=torch.float32, device=dev)
         g_w_sd, g_bias_sd, g_b_post, g_gamma, g_beta, g_w_post = gbuf[:sum(n_ops)].split(n_ops)
-        g_w_mix, g_b_mix = gbuf[n_flat:n_flat + Fo * Fo], gbuf[n_flat + ((Fo * Fo + 63) & ~63):]
+        g_w_mix, g_b_mix = gbuf[n_flat:n_flat + Fo * Fo], gbuf[n_flat + _up64(Fo * Fo):]
         G = _lib.DgnTowersGrads(g_out=g_out.data_ptr(), g_h=g_h.data_ptr(), g_w_sd=g_w_sd.data_ptr(), g_bias_sd=g_bias_sd.data_ptr(),
                                 g_w_post=g_w_post.data_ptr(), g_b_post=g_b_post.data_ptr(), g_gamma=g_gamma.data_ptr(),
                                 g_beta=g_beta.data_ptr(), g_w_mix=g_w_mix.data_ptr(), g_b_mix=g_b_mix.data_ptr())
-        stream = _lib.stream_ptr(dev)
-        _lib.check(lib.dgn_towers_layer_backward(C.byref(L), C.byref(G), stream), "dgn_towers_layer_backward")
+        _lib.check(lib.dgn_towers_layer_backward(C.byref(L), C.byref(G), _lib.stream_ptr(dev)), "dgn_towers_layer_backward")
         return (None, None, None, None, None, g_h, None, None, None, None, None, g_w_sd.view(2 * Fm, Fm), g_bias_sd, g_w_post.view(T, S * fo, K),
                 g_b_post, g_gamma, g_beta, g_w_mix.view(Fo, Fo), g_b_mix)
 
@@ -1195,17 +1178,10 @@ def towers_layer(graph: DGNGraph, plan: AggPlan, avg_log: float, w_edge, h, snor
     ``dropout``: None, or ``(p, key tensor, offset)`` of the towers' F.dropout (:275) as ``ops.dropout`` takes them.  ``id_slot``: the
     index of the identity scaler among the columns of ``scale`` (None: unknown; DgnTowersLayer.id_slot1)."""
     S = 1 if scale is None else scale.shape[1]
-    if snorm is not None:
-        snorm = snorm.reshape(-1).contiguous()
-    if scale is not None:
-        scale = scale.contiguous()
+    scale, _, snorm = _flat_operands(scale, None, snorm)
     drop = None if dropout is None else (float(dropout[0]), dropout[1], int(dropout[2]))
     cfg = (n_towers, f_in, f_out, S, bool(residual), float(momentum), float(eps), float(slope), drop, (0 if S == 1 else id_slot))
-    nbt = num_batches_tracked
-    if nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64 and nbt.is_contiguous() and nbt.numel() <= 256):
-        with torch.no_grad():
-            nbt.add_(1)
-        nbt = None
+    nbt = _kernel_counter(num_batches_tracked, 256)
     return _TowersLayer.apply(graph, plan, float(avg_log), w_edge, cfg, h, snorm, scale, running_mean, running_var, nbt,
                               w_sd, bias_sd, w_post.contiguous(), b_post, gamma, beta, w_mix, b_mix)
 
@@ -1462,9 +1438,7 @@ class _DenseLayer(torch.autograd.Function):
         n_aux = int(lib.dgn_dense_layer_agg_aux_bytes(C.byref(L))) if AGG_AUX else 0      # (see _TowersLayer)
         aux = torch.empty(n_aux, dtype=torch.uint8, device=dev) if n_aux else None
         L.agg_aux = _ptr(aux)
-        nbytes = lib.dgn_dense_layer_forward_workspace_bytes(C.byref(L))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        L.ws, L.ws_bytes = ws.data_ptr(), nbytes
+        ws = _layer_workspace(L, lib.dgn_dense_layer_forward_workspace_bytes(C.byref(L)), dev)
         stream = _lib.stream_ptr(dev)
         _lib.check(lib.dgn_dense_layer_forward(C.byref(L), stream), "dgn_dense_layer_forward")
         ctx.save_for_backward(w_edge, h, snorm, scale, w_pre, b_pre, w_post, b_post, gamma, beta, saved_buf, aux)
@@ -1486,9 +1460,7 @@ class _DenseLayer(torch.autograd.Function):
         L, keep = _dense_struct(graph, ctx.plan, ctx.avg_log, w_edge, cfg, h, snorm, scale, w_pre, b_pre, w_post, b_post, gamma, beta, bufs, ctx.n_valid,
                                 ctx.dc)
         L.agg_aux = _ptr(aux)
-        nbytes = lib.dgn_dense_layer_backward_workspace_bytes(C.byref(L))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        L.ws, L.ws_bytes = ws.data_ptr(), nbytes
+        ws = _layer_workspace(L, lib.dgn_dense_layer_backward_workspace_bytes(C.byref(L)), dev)
         g_h = torch.empty((N, F0), dtype=torch.float32, device=dev)
         n_pre = w_pre.numel() if w_pre is not None else 0
         _, (g_w_pre, g_b_pre, g_w_post, g_b_post, g_gamma, g_beta) = _carve([n_pre, F0 if (type_net == 1 and b_pre is not None) else 0, w_post.numel(), fo, fo, fo], dev)
@@ -1510,16 +1482,9 @@ def dense_layer(graph: DGNGraph, plan: AggPlan, avg_log: float, w_edge, h, snorm
     ``plan``: the sweep's list (with the h_in block last for the complex layer), identity scaler.  Training mode; the BatchNorm running
     statistics and ``num_batches_tracked`` are updated in place."""
     S = 1 if scale is None else scale.shape[1]
-    if snorm is not None:
-        snorm = snorm.reshape(-1).contiguous()
-    if scale is not None:
-        scale = scale.contiguous()
+    scale, _, snorm = _flat_operands(scale, None, snorm)
     cfg = (int(type_net), h.shape[1], w_post.shape[0], S, int(n_agg), int(id_slot), bool(residual), float(bn.momentum), float(bn.eps))
-    nbt = bn.num_batches_tracked
-    if nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64 and nbt.numel() == 1):
-        with torch.no_grad():
-            nbt.add_(1)
-        nbt = None
+    nbt = _kernel_counter(bn.num_batches_tracked, 1)
     return _DenseLayer.apply(graph, plan, float(avg_log), w_edge, cfg, h, snorm, scale, bn.running_mean, bn.running_var, nbt, w_pre, b_pre, w_post, b_post,
                              bn.weight, bn.bias)
 
