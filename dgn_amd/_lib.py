@@ -14,7 +14,7 @@ import threading
 DGN_MAX_AGG = 16
 DGN_MAX_CH = 4
 DGN_MAX_SCALERS = 4
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 LIB_PATH = os.environ.get("DGN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdgn_hip.so")
 
@@ -36,7 +36,9 @@ EXPORTS = ("dgn_abi_version", "dgn_sizeof", "dgn_last_error", "dgn_set_option", 
            "dgn_dc_supported", "dgn_dc_wgrad_supported", "dgn_dc_fold", "dgn_dc_gemm", "dgn_dc_wgrad_workspace_bytes", "dgn_dc_wgrad",
            "dgn_block_layer_supported", "dgn_block_layer_param_grad_floats", "dgn_block_layer_forward_workspace_bytes", "dgn_block_layer_forward",
            "dgn_block_layer_backward_workspace_bytes", "dgn_block_layer_backward",
-           "dgn_node_ce_workspace_bytes", "dgn_node_ce_forward", "dgn_node_ce_backward")
+           "dgn_node_ce_workspace_bytes", "dgn_node_ce_forward", "dgn_node_ce_backward",
+           "dgn_multi_embedding_supported", "dgn_multi_embedding_backward_workspace_bytes", "dgn_multi_embedding_forward", "dgn_multi_embedding_backward",
+           "dgn_masked_bce_workspace_bytes", "dgn_masked_bce_forward", "dgn_masked_bce_backward")
 
 DGN_DC_CLASSES, DGN_DC_UNIT = 32, 64
 
@@ -372,6 +374,21 @@ def load() -> C.CDLL:
         lib.dgn_node_ce_forward.argtypes = [C.c_int64, C.c_int32, vp, C.c_int64, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_size_t, vp]
         lib.dgn_node_ce_backward.restype = C.c_int
         lib.dgn_node_ce_backward.argtypes = [C.c_int64, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64, vp]
+        i32p = C.POINTER(C.c_int32)
+        lib.dgn_multi_embedding_supported.restype = C.c_int
+        lib.dgn_multi_embedding_supported.argtypes = [C.c_int32, i32p, C.c_int32]
+        lib.dgn_multi_embedding_backward_workspace_bytes.restype = C.c_size_t
+        lib.dgn_multi_embedding_backward_workspace_bytes.argtypes = [C.c_int64, C.c_int32, i32p, C.c_int32]
+        lib.dgn_multi_embedding_forward.restype = C.c_int
+        lib.dgn_multi_embedding_forward.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, C.POINTER(vp), i32p, vp, C.c_int64, vp]
+        lib.dgn_multi_embedding_backward.restype = C.c_int
+        lib.dgn_multi_embedding_backward.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, i32p, vp, C.c_int64, C.POINTER(vp), vp, C.c_size_t, vp]
+        lib.dgn_masked_bce_workspace_bytes.restype = C.c_size_t
+        lib.dgn_masked_bce_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+        lib.dgn_masked_bce_forward.restype = C.c_int
+        lib.dgn_masked_bce_forward.argtypes = [C.c_int64, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_size_t, vp]
+        lib.dgn_masked_bce_backward.restype = C.c_int
+        lib.dgn_masked_bce_backward.argtypes = [C.c_int64, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64, vp]
         if lib.dgn_abi_version() != ABI_VERSION:
             raise DgnError(f"libdgn_hip.so ABI {lib.dgn_abi_version()} != binding {ABI_VERSION}: rebuild")
         _lib = lib

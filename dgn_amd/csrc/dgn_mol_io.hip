@@ -1,0 +1,400 @@
+// Input encoders and loss of the OGB molecule nets (nets/HIV_graph_classification/dgn_net.py:41-44, :62, :68, :87-89 and
+// nets/PCBA_graph_classification/dgn_net.py:36-39, :67, :70, :99-102; train/train_PCBA_graph_classification.py:32-33): the sum of C
+// embedding lookups (OGB's AtomEncoder: nine tables, BondEncoder: three) forward and backward, and the binary cross-entropy with logits
+// over the labelled entries of a [G, T] label matrix in which NaN means "not measured".  Nothing read back, no floating-point atomics,
+// fixed-order reductions (the same input gives the same bits), every launch parameter a function of the shapes alone.
+//
+//   emb_forward           one thread per (row, 1 / 2 / 4 consecutive features): h = ((0 + T_0[i_0]) + T_1[i_1]) + ... in column order --
+//                         the very adds of the torch composition, so the result is bit-equal to it
+//   emb_backward_partial  one workgroup per contiguous row range, all C tables as one partial table in LDS; thread (c, f) owns column f of
+//                         table c and walks the range's rows in order: a column's adds are sequential, no two threads share an address
+//   emb_backward_fold     one thread per table element: the workgroups' partials added in workgroup order (fp64), written to table c
+//   bce_stats             one workgroup per contiguous element range: labelled count (integer) and the fp64 sum of the loss terms
+//   bce_rows              every workgroup folds the slots (count, loss), block 0 writes the loss; then the gradient of its range
+//   bce_scale             the autograd backward: g_saved * *g_loss
+//
+// The tables' pointers travel in the kernel arguments (a struct by value): the parameters stay the separate nn.Embedding weights of the
+// state_dict and a captured graph holds their addresses like every other parameter's.  Indices outside a table are clamped (memory-safe).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "dgn_common.hpp"
+
+namespace dgn {
+namespace mol_io {
+
+constexpr int kMaxCols = DGN_MULTI_EMBEDDING_MAX_COLS;
+constexpr int kLdsFloats = 160 * 1024 / 4;      // the partial tables of one workgroup: the CU's whole LDS (OGB atoms: 173 rows -> F <= 236)
+constexpr int kFwdThreads = 256;
+constexpr int kBwdThreads = 1024;               // C F columns to own (atoms at hidden 70: 630)
+constexpr int kMaxGroups = 256;
+constexpr int kMinRows = 64;                    // rows per workgroup at least: few partial tables to fold for small batches
+constexpr int kFoldThreads = 256;
+
+struct Tables {
+    const float* t[kMaxCols];
+    int dims[kMaxCols];
+};
+struct GradTables {
+    float* t[kMaxCols];
+    int dims[kMaxCols];
+    int off[kMaxCols + 1];                      // first row of table c in the combined partial table
+};
+
+struct EmbLayout {
+    int groups;
+    int64_t per;                                // rows per workgroup
+    int64_t total;                              // floats of the combined table
+    size_t bytes;
+};
+
+inline int64_t table_rows(int32_t n_cols, const int32_t* dims) {
+    int64_t rows = 0;
+    for (int c = 0; c < n_cols; ++c) rows += dims[c];
+    return rows;
+}
+
+inline bool emb_args_ok(int32_t n_cols, const int32_t* dims, int32_t F) {
+    if (n_cols < 1 || n_cols > kMaxCols || !dims || F < 1) return false;
+    for (int c = 0; c < n_cols; ++c)
+        if (dims[c] < 1) return false;
+    return true;
+}
+
+inline EmbLayout emb_layout(int64_t n_rows, int64_t total) {
+    EmbLayout L{};
+    int64_t g = (n_rows + kMinRows - 1) / kMinRows;
+    if (g > kMaxGroups) g = kMaxGroups;
+    if (g < 1) g = 1;
+    L.per = (n_rows + g - 1) / g;
+    if (L.per < 1) L.per = 1;
+    L.groups = (int)((n_rows + L.per - 1) / L.per);
+    if (L.groups < 1) L.groups = 1;
+    L.total = total;
+    L.bytes = (size_t)g * (size_t)total * sizeof(float);       // sized by the upper bound of `groups`
+    return L;
+}
+
+__device__ __forceinline__ int clamp_row(int64_t r, int dim) { return r < 0 ? 0 : (r >= dim ? dim - 1 : (int)r); }
+
+template <int VEC>
+__global__ __launch_bounds__(kFwdThreads) void emb_forward(int64_t N, int C, int F, const int64_t* __restrict__ idx, int64_t ld_idx, Tables tb,
+                                                           float* __restrict__ out, int64_t ld_out) {
+    const int fv = F / VEC;
+    const int64_t i = (int64_t)blockIdx.x * kFwdThreads + threadIdx.x;
+    if (i >= N * fv) return;
+    const int64_t n = i / fv;
+    const int f = (int)(i - n * fv) * VEC;
+    float acc[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+    const int64_t* ip = idx + n * ld_idx;
+    for (int c = 0; c < C; ++c) {
+        const int r = clamp_row(ip[c], tb.dims[c]);
+        float v[VEC];
+        ldv<VEC>(v, tb.t[c] + (int64_t)r * F + f);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[k] = acc[k] + v[k];
+    }
+    stv<VEC>(out + n * ld_out + f, acc);
+}
+
+__global__ __launch_bounds__(kBwdThreads) void emb_backward_partial(int64_t N, int C, int F, const int64_t* __restrict__ idx, int64_t ld_idx,
+                                                                     GradTables m, const float* __restrict__ g, int64_t ld_g, int64_t per,
+                                                                     float* __restrict__ part) {
+    extern __shared__ float s_tab[];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int total = m.off[C] * F;
+    for (int i = tid; i < total; i += kBwdThreads) s_tab[i] = 0.f;
+    __syncthreads();
+    const int64_t r0 = (int64_t)b * per, r1 = (r0 + per < N) ? r0 + per : N;
+    const int items = C * F;
+    for (int it = tid; it < items; it += kBwdThreads) {
+        const int c = it / F, f = it - c * F;
+        const int dim = m.dims[c];
+        float* tab = s_tab + m.off[c] * F + f;
+        const int64_t* ip = idx + c;
+        const float* gp = g + f;
+        int64_t n = r0;
+        for (; n + 4 <= r1; n += 4) {            // four rows' loads in flight, their adds in row order
+            int64_t a[4];
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { a[k] = ip[(n + k) * ld_idx]; v[k] = gp[(n + k) * ld_g]; }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float* p = tab + clamp_row(a[k], dim) * F;
+                *p = *p + v[k];
+            }
+        }
+        for (; n < r1; ++n) {
+            float* p = tab + clamp_row(ip[n * ld_idx], dim) * F;
+            *p = *p + gp[n * ld_g];
+        }
+    }
+    __syncthreads();
+    float* dst = part + (int64_t)b * total;
+    for (int i = tid; i < total; i += kBwdThreads) dst[i] = s_tab[i];
+}
+
+__global__ __launch_bounds__(kFoldThreads) void emb_backward_fold(int C, int F, int G, GradTables m, const float* __restrict__ part, int total) {
+    const int i = blockIdx.x * kFoldThreads + threadIdx.x;
+    if (i >= total) return;
+    double s = 0.0;
+#pragma unroll 8
+    for (int gidx = 0; gidx < G; ++gidx) s += (double)part[(int64_t)gidx * total + i];
+    const int row = i / F, f = i - row * F;
+    int c = 0;
+    while (c + 1 < C && row >= m.off[c + 1]) ++c;
+    m.t[c][(int64_t)(row - m.off[c]) * F + f] = (float)s;
+}
+
+// ---- masked binary cross-entropy with logits ----------------------------------------------------------------------------------------
+
+constexpr int kBceThreads = 256;
+constexpr int kBceWaves = kBceThreads / kWave;
+constexpr int kBceMaxGroups = 256;
+constexpr int kBceMinElems = 2048;              // elements per workgroup at least
+
+struct BceLayout {
+    int groups;
+    int64_t per;                                // elements per workgroup
+    size_t lossp, cnt, bytes;
+};
+
+inline BceLayout bce_layout(int64_t n) {
+    BceLayout L{};
+    int64_t g = (n + kBceMinElems - 1) / kBceMinElems;
+    if (g > kBceMaxGroups) g = kBceMaxGroups;
+    if (g < 1) g = 1;
+    L.per = (n + g - 1) / g;
+    if (L.per < 1) L.per = 1;
+    L.groups = (int)((n + L.per - 1) / L.per);
+    if (L.groups < 1) L.groups = 1;
+    L.lossp = 0;                                                // double [kBceMaxGroups]
+    L.cnt = L.lossp + kBceMaxGroups * sizeof(double);           // int64  [kBceMaxGroups]
+    L.bytes = L.cnt + kBceMaxGroups * sizeof(int64_t);
+    return L;
+}
+
+__device__ __forceinline__ double shfl_xor_d(double v, int o) { return __shfl_xor(v, o, kWave); }
+
+// fixed-shape tree over the workgroup: wave butterflies with lane-ordered operands, then the waves in order; the result on every thread
+__device__ __forceinline__ double block_sum(double v, double* s_red) {
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const double a2 = shfl_xor_d(v, o);
+        v = (lane_id() & o) ? a2 + v : v + a2;
+    }
+    if (lane_id() == 0) s_red[threadIdx.x / kWave] = v;
+    __syncthreads();
+    double t = s_red[0];
+#pragma unroll
+    for (int w = 1; w < kBceWaves; ++w) t += s_red[w];
+    return t;
+}
+
+__global__ __launch_bounds__(kBceThreads) void bce_stats(int64_t n, int T, const float* __restrict__ x, int64_t ld, const float* __restrict__ y,
+                                                          int64_t ld_y, int64_t per, double* __restrict__ lossp, int64_t* __restrict__ cnt) {
+    __shared__ double s_red[kBceWaves];
+    __shared__ unsigned long long s_cnt;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int64_t e0 = (int64_t)b * per, e1 = (e0 + per < n) ? e0 + per : n;
+    if (tid == 0) s_cnt = 0ull;
+    __syncthreads();
+    double acc = 0.0;
+    unsigned long long mine = 0ull;
+    for (int64_t i = e0 + tid; i < e1; i += kBceThreads) {
+        const int64_t r = i / T;
+        const int c = (int)(i - r * T);
+        const float xv = x[r * ld + c], yv = y[r * ld_y + c];
+        if (yv == yv) {                                          // labelled
+            const float term = (fmaxf(xv, 0.f) - xv * yv) + log1pf(expf(-fabsf(xv)));
+            acc += (double)term;
+            ++mine;
+        }
+    }
+    if (mine) atomicAdd(&s_cnt, mine);                           // (integer: exact in any order)
+    const double t = block_sum(acc, s_red);                      // (its barrier also orders the count)
+    if (tid == 0) { lossp[b] = t; cnt[b] = (int64_t)s_cnt; }
+}
+
+__global__ __launch_bounds__(kBceThreads) void bce_rows(int64_t n, int T, const float* __restrict__ x, int64_t ld, const float* __restrict__ y,
+                                                         int64_t ld_y, int64_t per, int G, const double* __restrict__ lossp,
+                                                         const int64_t* __restrict__ cnt, float* __restrict__ loss, float* __restrict__ g,
+                                                         int64_t ld_g) {
+    __shared__ double s_red[kBceWaves];
+    __shared__ unsigned long long s_cnt;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    if (tid == 0) s_cnt = 0ull;
+    __syncthreads();
+    if (tid < G && cnt[tid] > 0) atomicAdd(&s_cnt, (unsigned long long)cnt[tid]);      // G <= 256 = one slot per thread
+    const double total = block_sum(tid < G ? lossp[tid] : 0.0, s_red);
+    const int64_t labelled = (int64_t)s_cnt;
+    // no labelled entry: 0 / 0 = nan, the mean over an empty selection (train_PCBA_graph_classification.py:32-33)
+    if (b == 0 && tid == 0) *loss = (float)(total / (double)labelled);
+    if (!g) return;
+    const float nf = (float)labelled;
+    const int64_t e0 = (int64_t)b * per, e1 = (e0 + per < n) ? e0 + per : n;
+    for (int64_t i = e0 + tid; i < e1; i += kBceThreads) {
+        const int64_t r = i / T;
+        const int c = (int)(i - r * T);
+        const float xv = x[r * ld + c], yv = y[r * ld_y + c];
+        float gv = 0.f;                                          // unlabelled: exactly zero
+        if (yv == yv) {
+            const float e = expf(-fabsf(xv));                    // sigmoid without an overflow at either end
+            const float s = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+            gv = (s - yv) / nf;
+        }
+        g[r * ld_g + c] = gv;
+    }
+}
+
+__global__ __launch_bounds__(kBceThreads) void bce_scale(int64_t n, int T, const float* __restrict__ g, int64_t ld_g, const float* __restrict__ g_loss,
+                                                          float* __restrict__ out, int64_t ld_out) {
+    const int64_t i = (int64_t)blockIdx.x * kBceThreads + threadIdx.x;
+    if (i >= n) return;
+    const int64_t r = i / T;
+    const int c = (int)(i - r * T);
+    out[r * ld_out + c] = g[r * ld_g + c] * *g_loss;
+}
+
+}  // namespace mol_io
+}  // namespace dgn
+
+using namespace dgn;
+
+extern "C" int dgn_multi_embedding_supported(int32_t n_cols, const int32_t* dims, int32_t F) {
+    if (!mol_io::emb_args_ok(n_cols, dims, F)) return 0;
+    return mol_io::table_rows(n_cols, dims) * (int64_t)F <= mol_io::kLdsFloats ? 1 : 0;
+}
+
+extern "C" size_t dgn_multi_embedding_backward_workspace_bytes(int64_t n_rows, int32_t n_cols, const int32_t* dims, int32_t F) {
+    if (n_rows < 0 || n_rows > INT32_MAX || !dgn_multi_embedding_supported(n_cols, dims, F)) return 0;
+    return mol_io::emb_layout(n_rows, mol_io::table_rows(n_cols, dims) * F).bytes;
+}
+
+extern "C" int dgn_multi_embedding_forward(int64_t n_rows, int32_t n_cols, int32_t F, const int64_t* idx, int64_t ld_idx, const float* const* tables,
+                                           const int32_t* dims, float* out, int64_t ld_out, void* stream) {
+    if (!mol_io::emb_args_ok(n_cols, dims, F)) {
+        set_error("dgn_multi_embedding_forward: 1 <= n_cols <= %d tables of at least one row and F >= 1 required", mol_io::kMaxCols);
+        return DGN_ERR_INVALID;
+    }
+    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_multi_embedding_forward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    if (n_rows == 0) return DGN_OK;
+    if (!idx || !tables || !out) { set_error("dgn_multi_embedding_forward: null pointer"); return DGN_ERR_INVALID; }
+    if (ld_idx < n_cols || ld_out < F) { set_error("dgn_multi_embedding_forward: row stride below the row's width"); return DGN_ERR_INVALID; }
+    mol_io::Tables tb{};
+    uintptr_t align = reinterpret_cast<uintptr_t>(out) | (uintptr_t)(ld_out * sizeof(float)) | (uintptr_t)((int64_t)F * sizeof(float));
+    for (int c = 0; c < n_cols; ++c) {
+        if (!tables[c]) { set_error("dgn_multi_embedding_forward: null table %d", c); return DGN_ERR_INVALID; }
+        tb.t[c] = tables[c];
+        tb.dims[c] = dims[c];
+        align |= reinterpret_cast<uintptr_t>(tables[c]);
+    }
+    const int vec = (align & 15) == 0 ? 4 : ((align & 7) == 0 ? 2 : 1);     // 16-byte pieces where the rows allow them
+    const int64_t blocks = (n_rows * (F / vec) + mol_io::kFwdThreads - 1) / mol_io::kFwdThreads;
+    if (blocks > INT32_MAX) { set_error("dgn_multi_embedding_forward: n_rows x F beyond the grid range"); return DGN_ERR_INVALID; }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)blocks), block(mol_io::kFwdThreads);
+    if (vec == 4) hipLaunchKernelGGL(mol_io::emb_forward<4>, grid, block, 0, st, n_rows, n_cols, F, idx, ld_idx, tb, out, ld_out);
+    else if (vec == 2) hipLaunchKernelGGL(mol_io::emb_forward<2>, grid, block, 0, st, n_rows, n_cols, F, idx, ld_idx, tb, out, ld_out);
+    else hipLaunchKernelGGL(mol_io::emb_forward<1>, grid, block, 0, st, n_rows, n_cols, F, idx, ld_idx, tb, out, ld_out);
+    DGN_HIP_CHECK(hipGetLastError());
+    return DGN_OK;
+}
+
+extern "C" int dgn_multi_embedding_backward(int64_t n_rows, int32_t n_cols, int32_t F, const int64_t* idx, int64_t ld_idx, const int32_t* dims,
+                                            const float* g, int64_t ld_g, float* const* g_tables, void* ws, size_t ws_bytes, void* stream) {
+    if (!mol_io::emb_args_ok(n_cols, dims, F)) {
+        set_error("dgn_multi_embedding_backward: 1 <= n_cols <= %d tables of at least one row and F >= 1 required", mol_io::kMaxCols);
+        return DGN_ERR_INVALID;
+    }
+    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_multi_embedding_backward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    const int64_t total = mol_io::table_rows(n_cols, dims) * F;
+    if (total > mol_io::kLdsFloats) {
+        set_error("dgn_multi_embedding_backward: %lld table floats exceed the LDS budget of %d (dgn_multi_embedding_supported)", (long long)total,
+                  mol_io::kLdsFloats);
+        return DGN_ERR_INVALID;
+    }
+    if (!g_tables) { set_error("dgn_multi_embedding_backward: null pointer"); return DGN_ERR_INVALID; }
+    mol_io::GradTables m{};
+    for (int c = 0; c < n_cols; ++c) {
+        if (!g_tables[c]) { set_error("dgn_multi_embedding_backward: null gradient table %d", c); return DGN_ERR_INVALID; }
+        m.t[c] = g_tables[c];
+        m.dims[c] = dims[c];
+        m.off[c + 1] = m.off[c] + dims[c];
+    }
+    if (n_rows > 0 && (!idx || !g)) { set_error("dgn_multi_embedding_backward: null pointer"); return DGN_ERR_INVALID; }
+    if (n_rows > 0 && (ld_idx < n_cols || ld_g < F)) { set_error("dgn_multi_embedding_backward: row stride below the row's width"); return DGN_ERR_INVALID; }
+    const mol_io::EmbLayout L = mol_io::emb_layout(n_rows, total);
+    if (!ws || ws_bytes < L.bytes || (reinterpret_cast<uintptr_t>(ws) & 3)) {
+        set_error("dgn_multi_embedding_backward: workspace of %zu bytes required, got %zu", L.bytes, ws_bytes);
+        return DGN_ERR_INVALID;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    static bool attr = false;
+    if (!attr) {
+        DGN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mol_io::emb_backward_partial), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          mol_io::kLdsFloats * (int)sizeof(float)));
+        attr = true;
+    }
+    float* part = static_cast<float*>(ws);
+    // (no row: one workgroup leaves a zero partial table, the fold writes the zero gradients)
+    hipLaunchKernelGGL(mol_io::emb_backward_partial, dim3((unsigned)L.groups), dim3(mol_io::kBwdThreads), (size_t)total * sizeof(float), st, n_rows,
+                       n_cols, F, idx, ld_idx, m, g, ld_g, L.per, part);
+    hipLaunchKernelGGL(mol_io::emb_backward_fold, dim3((unsigned)((total + mol_io::kFoldThreads - 1) / mol_io::kFoldThreads)),
+                       dim3(mol_io::kFoldThreads), 0, st, n_cols, F, L.groups, m, (const float*)part, (int)total);
+    DGN_HIP_CHECK(hipGetLastError());
+    return DGN_OK;
+}
+
+extern "C" size_t dgn_masked_bce_workspace_bytes(int64_t n_rows, int32_t n_tasks) {
+    if (n_rows < 0 || n_tasks < 1 || n_rows > INT32_MAX) return 0;
+    return mol_io::bce_layout(n_rows * n_tasks).bytes;
+}
+
+extern "C" int dgn_masked_bce_forward(int64_t n_rows, int32_t n_tasks, const float* scores, int64_t ld, const float* labels, int64_t ld_y,
+                                      float* loss, float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes, void* stream) {
+    const int T = n_tasks;
+    if (T < 1) { set_error("dgn_masked_bce_forward: n_tasks >= 1 required (got %d)", T); return DGN_ERR_INVALID; }
+    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_masked_bce_forward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    if (!loss) { set_error("dgn_masked_bce_forward: null loss"); return DGN_ERR_INVALID; }
+    if (n_rows > 0 && (!scores || !labels)) { set_error("dgn_masked_bce_forward: null scores / labels"); return DGN_ERR_INVALID; }
+    if (ld < T || ld_y < T || (g_scores && ld_g < T)) { set_error("dgn_masked_bce_forward: row stride below n_tasks"); return DGN_ERR_INVALID; }
+    const int64_t n = n_rows * T;
+    if (n > (int64_t)INT32_MAX * 64) { set_error("dgn_masked_bce_forward: n_rows x n_tasks beyond the grid range"); return DGN_ERR_INVALID; }
+    const mol_io::BceLayout L = mol_io::bce_layout(n);
+    if (!ws || ws_bytes < L.bytes || (reinterpret_cast<uintptr_t>(ws) & 7)) {
+        set_error("dgn_masked_bce_forward: workspace of %zu bytes (8-byte aligned) required, got %zu", L.bytes, ws_bytes);
+        return DGN_ERR_INVALID;
+    }
+    char* base = static_cast<char*>(ws);
+    double* lossp = reinterpret_cast<double*>(base + L.lossp);
+    int64_t* cnt = reinterpret_cast<int64_t*>(base + L.cnt);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)L.groups), block(mol_io::kBceThreads);
+    // (no row: the one workgroup finds nothing labelled and the loss is nan, as the mean over an empty selection)
+    hipLaunchKernelGGL(mol_io::bce_stats, grid, block, 0, st, n, T, scores, ld, labels, ld_y, L.per, lossp, cnt);
+    hipLaunchKernelGGL(mol_io::bce_rows, g_scores ? grid : dim3(1), block, 0, st, n, T, scores, ld, labels, ld_y, L.per, L.groups,
+                       (const double*)lossp, (const int64_t*)cnt, loss, g_scores, ld_g);
+    DGN_HIP_CHECK(hipGetLastError());
+    return DGN_OK;
+}
+
+extern "C" int dgn_masked_bce_backward(int64_t n_rows, int32_t n_tasks, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
+                                       int64_t ld_out, void* stream) {
+    const int T = n_tasks;
+    if (T < 1) { set_error("dgn_masked_bce_backward: n_tasks >= 1 required (got %d)", T); return DGN_ERR_INVALID; }
+    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_masked_bce_backward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    if (n_rows == 0) return DGN_OK;
+    if (!g_saved || !g_loss || !g_scores) { set_error("dgn_masked_bce_backward: null pointer"); return DGN_ERR_INVALID; }
+    if (ld_g < T || ld_out < T) { set_error("dgn_masked_bce_backward: row stride below n_tasks"); return DGN_ERR_INVALID; }
+    const int64_t n = n_rows * T;
+    if (n > (int64_t)INT32_MAX * 64) { set_error("dgn_masked_bce_backward: n_rows x n_tasks beyond the grid range"); return DGN_ERR_INVALID; }
+    hipLaunchKernelGGL(mol_io::bce_scale, dim3((unsigned)((n + mol_io::kBceThreads - 1) / mol_io::kBceThreads)), dim3(mol_io::kBceThreads), 0,
+                       static_cast<hipStream_t>(stream), n, T, g_saved, ld_g, g_loss, g_scores, ld_out);
+    DGN_HIP_CHECK(hipGetLastError());
+    return DGN_OK;
+}

@@ -217,7 +217,7 @@ class CapturedNetStep:
         self.opt.zero_grad(set_to_none=True)
         self.pb.graph.invalidate_caches()
         scores = self.net(self.pb.graph, self.atoms, None, self.snorm, None)
-        loss = ((scores - self.targets).abs() * self.gmask).sum() / self.n_graphs
+        loss = self._loss(scores)
         loss.backward()
         self.opt.step()
         self.loss.copy_(loss.detach().reshape(()))
@@ -225,6 +225,10 @@ class CapturedNetStep:
         # released inside the NEXT capture region it would crash capture_end, see capture())
         self.pb.graph.ndata.pop("h", None)
         del scores, loss
+
+    def _loss(self, scores: torch.Tensor) -> torch.Tensor:
+        """The net's loss over the real graph rows (mean absolute error; the rows behind the batch are masked)."""
+        return ((scores - self.targets).abs() * self.gmask).sum() / self.n_graphs
 
     def capture(self, warmup: int = 3) -> None:
         """Capture the step on the batch currently loaded (the warm-up steps DO update the parameters)."""
@@ -237,6 +241,40 @@ class CapturedNetStep:
         else:
             self.graph.replay()
         return self.loss
+
+
+class CapturedMolStep(CapturedNetStep):
+    """``CapturedNetStep`` for the OGB molecule nets (``dgn_amd.nets.DGNHIVNet`` / ``DGNPCBANet``: AtomEncoder, L layers, readout, MLP,
+    binary cross-entropy over the labelled entries, backward, optimizer) -- the same padding scheme and static buffers, with two changes:
+    the atom buffer is ``[n_cap, 9]`` (one column per ogb atom feature; the padding rows carry zeros, a valid index of every table), and
+    the targets are a ``[g_rows, n_tasks]`` label buffer that holds NaN behind the batch, so that the loss kernel itself masks the padding
+    graph rows (``net.loss`` = ``ops.masked_bce_with_logits``: they count nowhere and their gradient rows are exactly zero).
+
+    Refused with a ValueError: ``edge_feat=True`` (as ``CapturedNetStep``), ``pos_enc_dim > 0`` (no static positional-encoding buffer), and
+    ``virtual_node`` (the VirtualNode layers' BatchNorm runs over the graph rows and would count the padding rows in its statistics, and
+    their broadcast to the nodes has a data-dependent size): run those nets eagerly."""
+
+    def __init__(self, net, n_cap: int, e_cap: int, g_cap: int, eig_dim: int, **kwargs):
+        if getattr(net, "pos_enc_dim", 0) > 0:
+            raise ValueError("CapturedMolStep: nets with pos_enc_dim > 0 are not supported (no static positional-encoding buffer)")
+        if getattr(net, "virtual_node_layers", None) is not None:
+            raise ValueError("CapturedMolStep: nets with virtual_node are not supported (the VirtualNode layers' BatchNorm over the graph rows "
+                             "would count the padding rows); run them eagerly or build the net with virtual_node=None")
+        super().__init__(net, n_cap, e_cap, g_cap, eig_dim, **kwargs)
+        n_cols = len(net.embedding_h.dims)
+        self.atoms = torch.zeros(self.pb.n_cap, n_cols, dtype=torch.int64, device=self.device)
+        self.targets = torch.full((self.g_rows, int(net.n_tasks)), float("nan"), device=self.device)
+
+    @torch.no_grad()
+    def load(self, src, dst, num_nodes: int, eig, atoms, snorm, sizes, labels) -> None:
+        """atoms [num_nodes, 9] int64; labels [n_graphs] or [n_graphs, n_tasks] of any dtype, NaN = not measured."""
+        G = len(sizes)
+        labels = torch.as_tensor(labels).to(device=self.device, dtype=torch.float32).reshape(G, -1)
+        super().load(src, dst, num_nodes, eig, atoms, snorm, sizes, labels)
+        self.targets[G:].fill_(float("nan"))
+
+    def _loss(self, scores: torch.Tensor) -> torch.Tensor:
+        return self.net.loss(scores, self.targets)
 
 
 class CapturedNodeStep:

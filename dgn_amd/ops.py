@@ -1899,3 +1899,142 @@ def balanced_cross_entropy(scores: torch.Tensor, labels: torch.Tensor, n_classes
     ``accuracy_SBM`` (train/metrics.py:37-40: rows = label, columns = arg-max over classes of the softmax over the NODES), see
     ``nets.accuracy_sbm``.  One class only among the labels: ``nan``, as the reference."""
     return _BalancedCrossEntropy.apply(scores, labels, int(n_classes), bool(confusion))
+
+
+# ---- OGB molecule nets: multi-column embedding sum, masked BCE with logits (dgn_mol_io.hip) ------------------------------------------
+
+MULTI_EMBEDDING_MAX_COLS = 16      # include/dgn_hip.h: DGN_MULTI_EMBEDDING_MAX_COLS
+
+
+def _i32_array(values):
+    return (C.c_int32 * len(values))(*values)
+
+
+def _ptr_array(tensors):
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def multi_embedding_supported(weights, idx=None) -> bool:
+    """Whether ``multi_embedding`` runs the fused kernels on tables of these SHAPES (at most 16 columns, all tables together within the
+    LDS budget of the backward: dgn_multi_embedding_supported); otherwise it is the torch composition."""
+    dims, F = [int(w.shape[0]) for w in weights], int(weights[0].shape[1])
+    if not 1 <= len(dims) <= MULTI_EMBEDDING_MAX_COLS:
+        return False
+    return bool(_lib.load().dgn_multi_embedding_supported(len(dims), _i32_array(dims), F))
+
+
+def multi_embedding_validate(weights, idx: torch.Tensor) -> None:
+    """Raise what ``nn.Embedding`` raises for an index outside its table (one host sync: for loaders and tests, once per dataset; the
+    kernels CLAMP such an index, which is memory-safe)."""
+    if idx.numel() == 0:
+        return
+    lo, hi = idx.min(dim=0).values.tolist(), idx.max(dim=0).values.tolist()
+    for c, w in enumerate(weights):
+        if lo[c] < 0 or hi[c] >= w.shape[0]:
+            raise IndexError(f"index out of range in self (column {c}: values in [{lo[c]}, {hi[c]}], table of {w.shape[0]} rows)")
+
+
+class _MultiEmbedding(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, idx, *weights):
+        lib = _lib.load()
+        N, n_cols = idx.shape
+        F = weights[0].shape[1]
+        weights = tuple(w.contiguous() for w in weights)
+        if idx.stride(1) != 1:
+            idx = idx.contiguous()
+        dims = _i32_array([int(w.shape[0]) for w in weights])
+        out = torch.empty(N, F, dtype=torch.float32, device=idx.device)
+        rc = lib.dgn_multi_embedding_forward(N, n_cols, F, idx.data_ptr(), idx.stride(0) if N > 1 else n_cols, _ptr_array(weights), dims,
+                                             out.data_ptr(), F, _lib.stream_ptr(idx.device))
+        _lib.check(rc, "dgn_multi_embedding_forward")
+        ctx.save_for_backward(idx)
+        ctx.dims, ctx.F = dims, F
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        (idx,) = ctx.saved_tensors
+        N, n_cols = idx.shape
+        F, dims, dev = ctx.F, ctx.dims, g.device
+        g = g.contiguous()
+        grads = [torch.empty(int(d), F, dtype=torch.float32, device=dev) for d in dims]
+        ws_bytes = lib.dgn_multi_embedding_backward_workspace_bytes(N, n_cols, dims, F)
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
+        rc = lib.dgn_multi_embedding_backward(N, n_cols, F, idx.data_ptr(), idx.stride(0) if N > 1 else n_cols, dims, g.data_ptr(), F,
+                                              _ptr_array(grads), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        _lib.check(rc, "dgn_multi_embedding_backward")
+        return (None,) + tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[1:]))
+
+
+def multi_embedding(weights, idx: torch.Tensor) -> torch.Tensor:
+    """``sum_c weights[c][idx[:, c]]`` -- ogb's AtomEncoder / BondEncoder (nets/HIV_graph_classification/dgn_net.py:62, :68): the C
+    ``nn.Embedding`` lookups and their adds as ONE launch, bit-equal to the torch loop ``h = 0; h += emb_c(idx[:, c])``, and the C weight
+    gradients as two launches over the upstream gradient (no sort, no floating-point atomics: reproducible bit for bit).  ``weights``:
+    C fp32 ``[dims[c], F]`` CUDA tensors (the separate ``nn.Embedding`` weights), ``idx`` int64 ``[N, C]``.  An index outside its table is
+    clamped (``multi_embedding_validate`` raises instead).  Shapes outside ``multi_embedding_supported`` run the torch composition."""
+    weights = tuple(weights)
+    if not idx.is_cuda or not all(w.is_cuda for w in weights):
+        raise _lib.DgnError("multi_embedding: CUDA tensors only (dgn_amd has no CPU path)")
+    if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[1] != len(weights):
+        raise ValueError(f"multi_embedding: idx must be int64 [N, {len(weights)}], got {idx.dtype} {tuple(idx.shape)}")
+    F = weights[0].shape[1]
+    if any(w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != F for w in weights):
+        raise ValueError("multi_embedding: the tables must be float32 [dims[c], F] with one common F")
+    if not multi_embedding_supported(weights):
+        h = 0
+        for c, w in enumerate(weights):
+            h = h + torch.nn.functional.embedding(idx[:, c], w)
+        return h
+    return _MultiEmbedding.apply(idx, *weights)
+
+
+class _MaskedBCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, labels):
+        lib = _lib.load()
+        if scores.stride(1) != 1:
+            scores = scores.contiguous()
+        labels = labels.contiguous()
+        G, T = scores.shape
+        dev = scores.device
+        want_grad = ctx.needs_input_grad[0]                   # (False under torch.no_grad(): no gradient buffer is written)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        g = torch.empty(G, T, dtype=torch.float32, device=dev) if want_grad else None
+        ws_bytes = lib.dgn_masked_bce_workspace_bytes(G, T)
+        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
+        rc = lib.dgn_masked_bce_forward(G, T, scores.data_ptr(), scores.stride(0) if G > 1 else T, labels.data_ptr(), T, out.data_ptr(), _ptr(g), T,
+                                        ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        _lib.check(rc, "dgn_masked_bce_forward")
+        ctx.save_for_backward(g)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        (g,) = ctx.saved_tensors
+        lib = _lib.load()
+        g_loss = g_loss.to(torch.float32).contiguous()
+        out = torch.empty_like(g)
+        rc = lib.dgn_masked_bce_backward(g.shape[0], g.shape[1], g.data_ptr(), g.stride(0), g_loss.data_ptr(), out.data_ptr(), out.stride(0),
+                                         _lib.stream_ptr(g.device))
+        _lib.check(rc, "dgn_masked_bce_backward")
+        return out, None
+
+
+def masked_bce_with_logits(scores: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """``BCEWithLogitsLoss()(scores[labelled], labels[labelled])`` with ``labelled = labels == labels`` (NaN = not measured), the loss of
+    the OGB molecule nets as their loops call it (train/train_PCBA_graph_classification.py:32-33, nets/PCBA_graph_classification/
+    dgn_net.py:99-102) without the boolean index: two launches, the labelled count taken on the device, nothing read back (capturable);
+    the backward is one launch.  ``scores`` float32 ``[G, T]`` (or 1-D), ``labels`` of the same shape and any dtype.  Labels without a NaN
+    give the plain mean; no labelled entry gives ``nan`` with an all-zero gradient, as the reference's two lines do."""
+    if not scores.is_cuda or not labels.is_cuda:
+        raise _lib.DgnError("masked_bce_with_logits: CUDA tensors only (dgn_amd has no CPU path)")
+    if scores.dim() == 1:
+        scores, labels = scores.unsqueeze(-1), labels.unsqueeze(-1)
+    if scores.dim() != 2 or scores.dtype != torch.float32 or labels.shape != scores.shape:
+        raise ValueError(f"masked_bce_with_logits: float32 scores [G, T] and labels of the same shape, got {scores.dtype} {tuple(scores.shape)} / "
+                         f"{tuple(labels.shape)}")
+    if scores.shape[1] == 0:
+        raise ValueError("masked_bce_with_logits: at least one task column")
+    return _MaskedBCE.apply(scores, labels.to(torch.float32))

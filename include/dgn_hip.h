@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DGN_ABI_VERSION 29
+#define DGN_ABI_VERSION 30
 
 #define DGN_MAX_AGG 16     /* aggregators per launch (the host splits longer lists)            */
 #define DGN_MAX_CH 4       /* edge-weight channels per launch                                   */
@@ -800,6 +800,41 @@ int dgn_node_ce_forward(int64_t n_rows, int32_t n_classes, const float* scores, 
                         float* weight, float* g_scores, int64_t ld_g, int64_t* confusion, void* ws, size_t ws_bytes, void* stream);
 int dgn_node_ce_backward(int64_t n_rows, int32_t n_classes, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
                          int64_t ld_out, void* stream);
+
+/* ---- OGB molecule nets: multi-column embedding sum + masked BCE with logits (dgn_mol_io.hip) ----------------------------------------
+ * Multi-column embedding sum.  Replaces ogb's AtomEncoder / BondEncoder as the nets call them (nets/HIV_graph_classification/
+ * dgn_net.py:41-44, :62, :68; nets/PCBA_graph_classification/dgn_net.py:36-39, :67, :70): C nn.Embedding lookups and C - 1 adds forward,
+ * C sort-based embedding_dense_backward passes backward.  idx [N, C] int64 (row stride ld_idx, unit column stride), 1 <= C <=
+ * DGN_MULTI_EMBEDDING_MAX_COLS; tables / g_tables: HOST arrays of C DEVICE pointers to fp32 [dims[c], F] dense tables (read at the call:
+ * they travel in the kernel arguments), dims: HOST array.  N < 2^31.  An index outside [0, dims[c]) is CLAMPED into the table.
+ *     forward   out[n, :] = ((0 + T_0[idx[n, 0]]) + T_1[idx[n, 1]]) + ...   plain fp32 adds in column order: bit-equal to the torch loop;
+ *               one launch; 8- / 16-byte accesses where F, the row stride and the pointers allow them; any C <= 16 and F
+ *     backward  g_tables[c][r, :] = sum_{n: idx[n, c] = r} g[n, :]  for all C tables in one pass over g, every element written (rows
+ *               without a hit: 0); two launches: per-workgroup partial tables in LDS over contiguous row ranges (a column's adds in row
+ *               order), then the partials added in workgroup order in fp64.  No floating-point atomics: the same input gives the same bits.
+ *               Needs sum(dims) * F floats of LDS: dgn_multi_embedding_supported says whether the shape fits (callers take another route
+ *               otherwise); ws: dgn_multi_embedding_backward_workspace_bytes bytes (0 for unsupported arguments).
+ * Masked BCE with logits.  Replaces the boolean-index selection in front of the loss and the loss itself (train/
+ * train_PCBA_graph_classification.py:32-33 + nets/PCBA_graph_classification/dgn_net.py:99-102; nets/HIV_graph_classification/
+ * dgn_net.py:87-89): the index is a device-to-host read-back per step and cannot be captured.  scores [G, T] fp32 (row stride ld),
+ * labels [G, T] fp32 (row stride ld_y), NaN = not labelled; G < 2^31.
+ *     loss      = mean over the labelled entries of max(x, 0) - x y + log1p(exp(-|x|))        DEVICE float; no labelled entry: nan
+ *     g_scores  = (sigmoid(x) - y) / n_labelled on labelled entries, exactly 0 elsewhere   [G, T] (row stride ld_g); NULL: not wanted
+ * The labelled count is taken on the device; cross-lane and cross-workgroup sums run in fp64 in an order that depends on (G, T) alone.
+ * Two launches; ws: 8-byte aligned, dgn_masked_bce_workspace_bytes bytes.  dgn_masked_bce_backward: the autograd backward, ONE launch:
+ * g_scores[r, t] = g_saved[r, t] * *g_loss (g_loss: DEVICE float).                                                                    */
+#define DGN_MULTI_EMBEDDING_MAX_COLS 16
+int dgn_multi_embedding_supported(int32_t n_cols, const int32_t* dims, int32_t F);
+size_t dgn_multi_embedding_backward_workspace_bytes(int64_t n_rows, int32_t n_cols, const int32_t* dims, int32_t F);
+int dgn_multi_embedding_forward(int64_t n_rows, int32_t n_cols, int32_t F, const int64_t* idx, int64_t ld_idx, const float* const* tables,
+                                const int32_t* dims, float* out, int64_t ld_out, void* stream);
+int dgn_multi_embedding_backward(int64_t n_rows, int32_t n_cols, int32_t F, const int64_t* idx, int64_t ld_idx, const int32_t* dims,
+                                 const float* g, int64_t ld_g, float* const* g_tables, void* ws, size_t ws_bytes, void* stream);
+size_t dgn_masked_bce_workspace_bytes(int64_t n_rows, int32_t n_tasks);
+int dgn_masked_bce_forward(int64_t n_rows, int32_t n_tasks, const float* scores, int64_t ld, const float* labels, int64_t ld_y, float* loss,
+                           float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes, void* stream);
+int dgn_masked_bce_backward(int64_t n_rows, int32_t n_tasks, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
+                            int64_t ld_out, void* stream);
 
 #ifdef __cplusplus
 }
