@@ -21,7 +21,9 @@ from .readout import VirtualNode, readout
 
 
 class MLPReadout(nn.Module):
-    """``L`` hidden Linear + ReLU layers (widths halving when ``decreasing_dim``) and an output Linear; keys ``FC_layers.{i}.*``."""
+    """``L`` hidden Linear + ReLU layers (widths halving when ``decreasing_dim``) and an output Linear; keys ``FC_layers.{i}.*``.  On the
+    device the whole head is ``ops.mlp_head``: one launch forward, two backward (widths up to 128, up to four Linears); other shapes, CPU
+    tensors and ``ops.FUSED_MLP_HEAD = False`` run the ``nn.Linear`` loop."""
 
     def __init__(self, input_dim: int, output_dim: int, L: int = 2, decreasing_dim: bool = True):
         super().__init__()
@@ -31,6 +33,10 @@ class MLPReadout(nn.Module):
         self.L = L
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from . import ops
+        weights = [fc.weight for fc in self.FC_layers]
+        if ops.FUSED_MLP_HEAD and ops.mlp_head_supported(x, weights):
+            return ops.mlp_head(x, weights, [fc.bias for fc in self.FC_layers])
         for fc in self.FC_layers[:-1]:
             x = F.relu(fc(x))
         return self.FC_layers[-1](x)
@@ -105,7 +111,8 @@ class DGNNodeNet(nn.Module):
     embedding, ``L`` DGN layers, a per-node ``MLPReadout`` to ``n_classes`` scores.  Same constructor dictionary, ``forward`` signature and
     ``state_dict`` keys (``embedding_h``, optional ``embedding_pos_enc``, ``layers.{i}.*``, ``MLP_layer.FC_layers.{i}.*``).  ``loss`` is the
     reference's batch-balanced cross-entropy (:67-81) as ``ops.balanced_cross_entropy``: three launches, no host read-back.  The MLP head
-    stays on torch's GEMMs (widths such as 47 -> 23 -> 11 -> 2 are outside the tall-skinny Linear's shapes).  Parity: fixture G11
+    (widths such as 47 -> 23 -> 11 -> 2, outside the tall-skinny Linear's shapes) is ``ops.mlp_head``: one launch on every node forward,
+    two backward.  Parity: fixture G11
     (tests/golden/make_golden_node.py), produced by the unmodified reference net."""
 
     def __init__(self, net_params: dict):

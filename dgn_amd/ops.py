@@ -2038,3 +2038,87 @@ def masked_bce_with_logits(scores: torch.Tensor, labels: torch.Tensor) -> torch.
     if scores.shape[1] == 0:
         raise ValueError("masked_bce_with_logits: at least one task column")
     return _MaskedBCE.apply(scores, labels.to(torch.float32))
+
+
+# ---- the nets' MLPReadout head in one launch per direction (dgn_mlp_head.hip) ---------------------------------------------------------
+
+# The one switch (DGN_FUSED_MLP_HEAD=0 / False: nets.MLPReadout runs its nn.Linear loop on torch's GEMMs): it puts the torch composition
+# next to the kernel within one process, for tools/mlp_head_time.py and the tests.
+FUSED_MLP_HEAD = os.environ.get("DGN_FUSED_MLP_HEAD", "1") != "0"
+
+_MLP_HEAD_OK = {}
+
+
+def _mlp_head_dims(weights):
+    return (int(weights[0].shape[1]),) + tuple(int(w.shape[0]) for w in weights)
+
+
+def mlp_head_supported(x: torch.Tensor, weights) -> bool:
+    """Whether ``mlp_head`` takes these tensors: CUDA float32 2-D ``x`` with unit column stride (a column slice of a wider tensor is fine)
+    and 1 to 4 chained ``[out, in]`` weights of widths 1 .. 128 with at most 20 480 elements together (dgn_mlp_head_supported)."""
+    weights = tuple(weights)
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and 1 <= len(weights) <= 4):
+        return False
+    if any(w.dim() != 2 or w.dtype != torch.float32 or not w.is_cuda for w in weights):
+        return False
+    dims = _mlp_head_dims(weights)
+    if x.shape[1] != dims[0] or any(w.shape[1] != d for w, d in zip(weights, dims)) or (x.shape[0] > 1 and x.stride(0) < dims[0]):
+        return False
+    if dims not in _MLP_HEAD_OK:
+        _MLP_HEAD_OK[dims] = bool(_lib.load().dgn_mlp_head_supported(len(weights), _i32_array(dims)))
+    return _MLP_HEAD_OK[dims]
+
+
+class _MLPHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, n_lin, *params):
+        lib = _lib.load()
+        weights, biases = tuple(w.contiguous() for w in params[:n_lin]), tuple(b.contiguous() for b in params[n_lin:])
+        dims = _mlp_head_dims(weights)
+        N, dev = x.shape[0], x.device
+        y = torch.empty(N, dims[-1], dtype=torch.float32, device=dev)
+        rc = lib.dgn_mlp_head_forward(N, n_lin, _i32_array(dims), x.data_ptr(), x.stride(0) if N > 1 else dims[0], _ptr_array(weights),
+                                      _ptr_array(biases), y.data_ptr(), dims[-1], _lib.stream_ptr(dev))
+        _lib.check(rc, "dgn_mlp_head_forward")
+        ctx.save_for_backward(x, *weights, *biases)           # (x and the parameters only: the backward computes the hidden activations again)
+        ctx.dims = dims
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_y):
+        lib = _lib.load()
+        x, *params = ctx.saved_tensors
+        dims = ctx.dims
+        n_lin = len(dims) - 1
+        weights, biases = params[:n_lin], params[n_lin:]
+        N, dev = x.shape[0], x.device
+        g_y = g_y.contiguous()
+        g_x = torch.empty(N, dims[0], dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        g_w, g_b = [torch.empty_like(w) for w in weights], [torch.empty_like(b) for b in biases]
+        c_dims = _i32_array(dims)
+        ws_bytes = lib.dgn_mlp_head_backward_workspace_bytes(N, n_lin, c_dims)
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
+        rc = lib.dgn_mlp_head_backward(N, n_lin, c_dims, x.data_ptr(), x.stride(0) if N > 1 else dims[0], _ptr_array(weights), _ptr_array(biases),
+                                       g_y.data_ptr(), dims[-1], _ptr(g_x), dims[0], _ptr_array(g_w), _ptr_array(g_b), ws.data_ptr(), ws_bytes,
+                                       _lib.stream_ptr(dev))
+        _lib.check(rc, "dgn_mlp_head_backward")
+        return (g_x, None) + tuple(g if need else None for g, need in zip(g_w + g_b, ctx.needs_input_grad[2:]))
+
+
+def mlp_head(x: torch.Tensor, weights, biases) -> torch.Tensor:
+    """``MLPReadout`` (nets/mlp_readout_layer.py:24-30) as ONE launch forward and two backward: ``h = relu(h W_l^T + b_l)`` for all but the
+    last ``(W_l, b_l)``, then ``h W_L^T + b_L``, a tile's activations in LDS between the Linears.  ``weights``: 1 to 4 fp32 ``[out, in]`` CUDA
+    tensors (the ``nn.Linear`` weights as they are), ``biases`` their ``[out]`` biases, ``x`` fp32 ``[N, in_0]`` with unit column stride.
+    Autograd keeps ``x`` and the parameters only; the backward writes no ``g_x`` when ``x`` needs none; no floating-point atomics (the same
+    input gives the same bits), no host read-back (capturable).  Shapes outside ``mlp_head_supported`` raise ``ValueError``: the caller
+    (``nets.MLPReadout``) asks first and runs torch's composition there."""
+    weights, biases = tuple(weights), tuple(biases)
+    if not x.is_cuda or not all(t.is_cuda for t in weights + biases):
+        raise _lib.DgnError("mlp_head: CUDA tensors only (dgn_amd has no CPU path)")
+    if len(biases) != len(weights) or any(b.dtype != torch.float32 or b.shape != (w.shape[0],) for w, b in zip(weights, biases)):
+        raise ValueError("mlp_head: one float32 [out] bias per [out, in] weight")
+    if not mlp_head_supported(x, weights):
+        raise ValueError(f"mlp_head: float32 x [N, in] with unit column stride and 1 to 4 chained weights of widths 1 .. 128 (at most 20480 "
+                         f"elements) required (mlp_head_supported), got x {x.dtype} {tuple(x.shape)} and weights {[tuple(w.shape) for w in weights]}")
+    return _MLPHead.apply(x, len(weights), *weights, *biases)

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DGN_ABI_VERSION 30
+#define DGN_ABI_VERSION 31
 
 #define DGN_MAX_AGG 16     /* aggregators per launch (the host splits longer lists)            */
 #define DGN_MAX_CH 4       /* edge-weight channels per launch                                   */
@@ -835,6 +835,27 @@ int dgn_masked_bce_forward(int64_t n_rows, int32_t n_tasks, const float* scores,
                            float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes, void* stream);
 int dgn_masked_bce_backward(int64_t n_rows, int32_t n_tasks, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
                             int64_t ld_out, void* stream);
+
+/* ---- the nets' MLP head in one launch per direction (dgn_mlp_head.hip) ---------------------------------------------------------------
+ * Replaces MLPReadout.forward of nets/mlp_readout_layer.py:24-30 (L hidden Linear + ReLU, then an output Linear: three addmm and two ReLU
+ * launches forward, about a dozen backward) by one launch forward and two backward.  n_linears = L + 1 in 1 .. 4; dims: HOST array of the
+ * n_linears + 1 widths, each in 1 .. 128, sum_l dims[l] dims[l + 1] <= 20 480 (dgn_mlp_head_supported: 1 inside this domain; callers
+ * take torch's route outside it).  w / b / g_w / g_b: HOST arrays of n_linears DEVICE pointers to dense fp32 [dims[l + 1], dims[l]] /
+ * [dims[l + 1]] tensors (torch's layout; read at the call: they travel in the kernel arguments).  x [n_rows, dims[0]], y and g_y
+ * [n_rows, dims[n_linears]], g_x as x: fp32, unit column stride, row strides ld_* >= the width, any 4-byte-aligned base.  n_rows < 2^31.
+ *     forward   y = W_L relu(... relu(W_1 x + b_1) ...) + b_L, a tile's activations in LDS between the Linears; every dot product starts
+ *               at its bias and takes its terms in increasing k with fmaf.  n_rows == 0: nothing to do.
+ *     backward  the hidden activations are computed again from x as the forward computed them (nothing else is kept); a ReLU passes the
+ *               gradient where its activation is > 0.  g_x: NULL = not wanted.  g_w / g_b are WRITTEN (n_rows == 0: zeros): per-workgroup
+ *               partials in ws, added in workgroup order in fp64 by the second launch.  No floating-point atomics: the same input gives
+ *               the same bits.  ws: 4-byte aligned, dgn_mlp_head_backward_workspace_bytes bytes (0 for arguments out of range). */
+int dgn_mlp_head_supported(int32_t n_linears, const int32_t* dims);      /* nets/mlp_readout_layer.py:24-30 */
+int dgn_mlp_head_forward(int64_t n_rows, int32_t n_linears, const int32_t* dims, const float* x, int64_t ld_x, const float* const* w,
+                         const float* const* b, float* y, int64_t ld_y, void* stream);      /* nets/mlp_readout_layer.py:24-30 */
+size_t dgn_mlp_head_backward_workspace_bytes(int64_t n_rows, int32_t n_linears, const int32_t* dims);
+int dgn_mlp_head_backward(int64_t n_rows, int32_t n_linears, const int32_t* dims, const float* x, int64_t ld_x, const float* const* w,
+                          const float* const* b, const float* g_y, int64_t ld_gy, float* g_x, int64_t ld_gx, float* const* g_w,
+                          float* const* g_b, void* ws, size_t ws_bytes, void* stream);      /* autograd of nets/mlp_readout_layer.py:24-30 */
 
 #ifdef __cplusplus
 }
