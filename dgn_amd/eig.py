@@ -33,11 +33,18 @@ def laplacian_eigvecs(src: torch.Tensor, dst: torch.Tensor, sizes: Sequence[int]
     """``[N, k]`` fp32: column j is the eigenvector of the j-th smallest eigenvalue of every graph's Laplacian (what
     ``get_eig(pos_enc_dim=k)`` stores, molecules.py:100-116); graphs with fewer than k nodes get zero columns.
     ``src``/``dst``: edges of the batched graph (global node ids, graphs occupy consecutive ranges ``sizes``)."""
+    return _bucketed_eigh(src, dst, sizes, k, norm, bucket)[0]
+
+
+def _bucketed_eigh(src: torch.Tensor, dst: torch.Tensor, sizes: Sequence[int], k: int, norm: str = "none", bucket: int = 8):
+    """``laplacian_eigvecs`` and the eigenvalues of the same ``eigh`` calls: ``(eig [N, k] fp32, values [G, k] fp64, NaN
+    beyond a graph's size)``."""
     if norm not in ("none", "sym", "walk"):
         raise ValueError(norm)
     dev = src.device
     sizes_t = torch.as_tensor(list(sizes), dtype=torch.long, device=dev)
     G, N = sizes_t.numel(), int(sizes_t.sum().item())
+    vals = torch.full((G, k), float("nan"), dtype=torch.float64, device=dev)
     off = torch.zeros(G + 1, dtype=torch.long, device=dev)
     off[1:] = torch.cumsum(sizes_t, 0)
     gid = torch.repeat_interleave(torch.arange(G, device=dev), sizes_t)            # node -> graph
@@ -68,7 +75,7 @@ def laplacian_eigvecs(src: torch.Tensor, dst: torch.Tensor, sizes: Sequence[int]
         L[nb, ni, ni] += diag
         pad = torch.arange(w, device=dev).unsqueeze(0) >= sizes_t[sel].unsqueeze(1)  # [g, w] padding positions
         L[:, torch.arange(w), torch.arange(w)] += pad.double() * _PAD
-        _, vec = torch.linalg.eigh(L)                                                # ascending eigenvalues
+        lam, vec = torch.linalg.eigh(L)                                              # ascending eigenvalues
         kk = min(k, w)
         v = vec[:, :, :kk]                                                           # [g, w, kk]
         if norm == "walk":
@@ -79,7 +86,121 @@ def laplacian_eigvecs(src: torch.Tensor, dst: torch.Tensor, sizes: Sequence[int]
         valid = (torch.arange(kk, device=dev).unsqueeze(0) < sizes_t[sel].unsqueeze(1)).unsqueeze(1)   # fewer nodes than k
         v = torch.where(valid, v, torch.zeros_like(v))
         out[n_ok, :kk] = v[nb, ni].float()
-    return out
+        vals[sel, :kk] = torch.where(valid.squeeze(1), lam[:, :kk], torch.full_like(lam[:, :kk], float("nan")))
+    return out, vals
+
+
+# ---- small graphs: the whole batch in one Jacobi kernel (csrc/dgn_eig_small.hip) ------------------------------------------
+
+_NORMS = {"none": 0, "sym": 1, "walk": 2}        # include/dgn_hip.h: DGN_EIG_NORM_*
+
+
+def laplacian_eig_small(graph, graph_offsets: torch.Tensor, k: int, norm: str = "none", *, out: Optional[torch.Tensor] = None,
+                        values: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, max_sweeps: int = 30):
+    """The thin launch of ``dgn_eig_small``: the ``k`` lowest Laplacian eigenpairs of every graph of at most 64 nodes, one
+    workgroup per graph, nothing read back (usable under ``torch.cuda.graph``).  ``graph``: a ``DGNGraph`` of the batch;
+    ``graph_offsets``: device int64 ``[G + 1]`` node offsets.  Returns ``(vec [N, k] fp32, values [G, k] fp64, status [G]
+    int32)``: ``status`` is the number of Jacobi sweeps, ``-1`` for a graph of more than 64 nodes, ``-2`` for one with an
+    edge from outside its node range -- the rows of such graphs keep what ``out`` / ``values`` held (zeros / NaN when the
+    buffers are made here)."""
+    from . import _lib
+    import ctypes as C
+    if norm not in _NORMS:
+        raise ValueError(norm)
+    dev = graph.device
+    if graph_offsets.dtype != torch.int64 or graph_offsets.device != dev or not graph_offsets.is_contiguous() or graph_offsets.dim() != 1:
+        raise ValueError("graph_offsets: a contiguous int64 [G + 1] tensor on the graph's device")
+    G, N = graph_offsets.numel() - 1, graph.num_nodes
+    if out is None:
+        out = torch.zeros(N, k, dtype=torch.float32, device=dev)
+    if values is None:
+        values = torch.full((G, k), float("nan"), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(G, dtype=torch.int32, device=dev)
+    for t, shape, dt in ((out, (N, k), torch.float32), (values, (G, k), torch.float64), (status, (G,), torch.int32)):
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"laplacian_eig_small: a buffer is not a contiguous {dt} {shape} tensor on {dev}")
+    _lib.check(_lib.load().dgn_eig_small(C.byref(graph.c_graph), graph_offsets.data_ptr(), G, int(k), _NORMS[norm], int(max_sweeps),
+                                         out.data_ptr(), values.data_ptr(), status.data_ptr(), _lib.stream_ptr(dev)), "dgn_eig_small")
+    return out, values, status
+
+
+def _eigh_fallback(graph, off: torch.Tensor, big, k: int, norm: str, eig: torch.Tensor, values: torch.Tensor) -> None:
+    """Fill the rows and eigenvalues of the graphs ``big`` (more than 64 nodes) from the bucketed ``eigh`` on their sub-batch."""
+    dev = graph.device
+    G = off.numel() - 1
+    sizes = off[1:] - off[:-1]
+    pick = torch.zeros(G, dtype=torch.bool)
+    pick[big] = True
+    keep = torch.repeat_interleave(pick, sizes).to(dev)                               # node -> belongs to a big graph
+    new_id = torch.cumsum(keep, 0) - 1
+    dst = torch.repeat_interleave(torch.arange(graph.num_nodes, device=dev), (graph.indptr[1:] - graph.indptr[:-1]).long())
+    src = graph.src.long()[:dst.numel()]
+    m = keep[dst]
+    v, lam = _bucketed_eigh(new_id[src[m]], new_id[dst[m]], sizes[big].tolist(), k, norm)
+    eig[keep] = v
+    values[torch.as_tensor(big, device=dev)] = lam
+
+
+def batch_eig(graph, sizes=None, k: int = 6, norm: str = "none", check: bool = True, *, max_sweeps: int = 30):
+    """``(eig [N, k] fp32, values [G, k] fp64)``: the k lowest Laplacian eigenvectors of every graph of a batch -- what
+    ``get_eig`` stores in ``g.ndata['eig']`` (data/molecules.py:100-116) -- and their eigenvalues (``get_eig_val``,
+    data/multiplicity_eig.py:14-27).  ``graph``: a ``DGNGraph`` or anything ``as_dgn_graph`` accepts; ``sizes``: the graphs'
+    node counts (host list or tensor; default: the graph's ``batch_num_nodes``).  Graphs of at most 64 nodes are solved by
+    ``dgn_eig_small`` in one launch pair.  ``check=True`` reads the statuses back once: an edge from outside a graph's node
+    range or a solve that did not converge raises, graphs of more than 64 nodes go through ``laplacian_eigvecs``.
+    ``check=False`` reads nothing back: the rows of such graphs stay zero, their eigenvalues NaN."""
+    from . import _lib
+    from .graph import DGNGraph, as_dgn_graph
+    if norm not in _NORMS:
+        raise ValueError(norm)
+    if not isinstance(graph, DGNGraph):
+        if sizes is None:
+            sizes = getattr(graph, "batch_num_nodes", None)
+        graph = as_dgn_graph(graph)
+    if sizes is None:
+        sizes = getattr(graph, "batch_num_nodes", None)
+    if callable(sizes):
+        sizes = sizes()
+    if sizes is None:
+        raise ValueError("batch_eig: pass the graphs' sizes (the graph carries no batch_num_nodes)")
+    sizes_t = torch.as_tensor(sizes, dtype=torch.int64).flatten()
+    off = torch.zeros(sizes_t.numel() + 1, dtype=torch.int64)
+    off[1:] = torch.cumsum(sizes_t, 0)
+    if int(off[-1]) != graph.num_nodes:
+        raise ValueError(f"batch_eig: the sizes add up to {int(off[-1])} nodes, the graph has {graph.num_nodes}")
+    eig, values, status = laplacian_eig_small(graph, off.to(graph.device), k, norm, max_sweeps=max_sweeps)
+    if not check:
+        return eig, values
+    st = status.cpu()
+    bad = torch.nonzero(st == -2).flatten().tolist()
+    if bad:
+        raise _lib.DgnError(f"batch_eig: graph {bad[0]} has an edge whose source lies outside its node range"
+                            + (f" (and {len(bad) - 1} more graphs)" if len(bad) > 1 else ""))
+    slow = torch.nonzero(st >= max_sweeps).flatten().tolist()
+    if slow:
+        raise _lib.DgnError(f"batch_eig: the Jacobi solve of graph {slow[0]} did not converge in {max_sweeps} sweeps (max_sweeps= raises the cap)")
+    big = torch.nonzero(st == -1).flatten().tolist()
+    if big:
+        _eigh_fallback(graph, off, big, k, norm, eig, values)
+    return eig, values
+
+
+def positional_encoding(graph, sizes=None, pos_enc_dim: int = 2) -> torch.Tensor:
+    """``[N, pos_enc_dim]`` fp32: eigenvectors 1 .. pos_enc_dim of the symmetric normalised Laplacian, the reference's
+    ``positional_encoding`` (data/molecules.py:18-32; its ``pos_enc`` of :118-121 is the same slice of ``eig``)."""
+    return batch_eig(graph, sizes, k=pos_enc_dim + 1, norm="sym")[0][:, 1:]
+
+
+def eig_multiplicity(values: torch.Tensor, first: int = 1, second: int = 2, tol: float = 1e-3):
+    """``(fraction, count, n)``: the graphs whose eigenvalues ``first`` and ``second`` differ by more than ``tol`` -- the
+    reference's check that a direction is well defined on a dataset (data/multiplicity_eig.py:52-55).  ``values``: ``[G, k]``
+    as ``batch_eig`` returns it; a NaN slot (fewer nodes than eigenvalues asked for) counts as not distinct.  Pure torch."""
+    n = int(values.shape[0])
+    if n == 0:
+        return 0.0, 0, 0
+    count = int((torch.abs(values[:, first] - values[:, second]) > tol).sum())      # (NaN > tol is False)
+    return count / n, count, n
 
 
 # ---- iterative solver for graphs that cannot be densified ---------------------------------------------------------------

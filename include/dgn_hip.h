@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DGN_ABI_VERSION 31
+#define DGN_ABI_VERSION 32
 
 #define DGN_MAX_AGG 16     /* aggregators per launch (the host splits longer lists)            */
 #define DGN_MAX_CH 4       /* edge-weight channels per launch                                   */
@@ -856,6 +856,26 @@ size_t dgn_mlp_head_backward_workspace_bytes(int64_t n_rows, int32_t n_linears, 
 int dgn_mlp_head_backward(int64_t n_rows, int32_t n_linears, const int32_t* dims, const float* x, int64_t ld_x, const float* const* w,
                           const float* const* b, const float* g_y, int64_t ld_gy, float* g_x, int64_t ld_gx, float* const* g_w,
                           float* const* g_b, void* ws, size_t ws_bytes, void* stream);      /* autograd of nets/mlp_readout_layer.py:24-30 */
+
+/* ---- Laplacian eigenpairs of a batch of small graphs in one Jacobi kernel (dgn_eig_small.hip) ------------------------------------------
+ * Replaces, for graphs of at most 64 nodes, the per-graph CPU solves of the reference's loaders: get_eig (data/molecules.py:100-116),
+ * positional_encoding (data/molecules.py:18-32) and get_eig_val of the multiplicity check (data/multiplicity_eig.py:14-27).
+ * graph: the batch's destination-major CSR (indptr, src; graphs occupy consecutive node ranges); graph_off: DEVICE [n_graphs + 1] node
+ * offsets.  Per graph the kernel forms L in fp64 -- in-degrees from indptr clipped to 1, adjacency symmetrised to (A + A^T) / 2, multi-edges
+ * and self-loops adding up; DGN_EIG_NORM_NONE: D - A, _SYM: I - D^-1/2 A D^-1/2, _WALK: the _SYM solve with the kept eigenvectors scaled by
+ * D^-1/2 and brought back to unit length -- and diagonalises it by cyclic Jacobi rotations until the off-diagonal Frobenius norm is
+ * <= 1e-14 ||L||_F or max_sweeps sweeps are done.
+ *     vec     [n_nodes, k] fp32, dense rows: the min(k, n) eigenvectors of lowest eigenvalue (ascending, ties by column index; signs as the
+ *             rotations leave them, the same bits for the same graph in any batch), further columns of the graph's rows 0
+ *     val     [n_graphs, k] fp64 or NULL: their eigenvalues, further slots NaN
+ *     status  [n_graphs]: sweeps done (>= 1; == max_sweeps: the stop rule was not met), -1: more than 64 nodes (the second function's
+ *             value), -2: an edge source outside the graph's node range, or a node range outside the CSR.  A graph with a negative status
+ *             has nothing else written: its rows of vec and val are as they were.
+ * 1 <= k <= 32.  Two launches over all graphs (<= 32 nodes: 64 threads, <= 64: 256), nothing read back, capturable.  n_graphs == 0: no-op. */
+enum { DGN_EIG_NORM_NONE = 0, DGN_EIG_NORM_SYM = 1, DGN_EIG_NORM_WALK = 2 };
+int dgn_eig_small(const DgnGraph* graph, const int64_t* graph_off, int n_graphs, int k, int norm, int max_sweeps, float* vec, double* val,
+                  int32_t* status, void* stream);
+int dgn_eig_small_max_nodes(void);
 
 #ifdef __cplusplus
 }
