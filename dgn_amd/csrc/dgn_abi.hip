@@ -1,4 +1,4 @@
-// Error plumbing and version of libdgn_hip.so.
+// Host plumbing of libdgn_hip.so: errors, options, version, and what the units' launch code shares (zero fill, loss scale, LDS opt-in).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -29,6 +29,15 @@ __global__ void zero_rows_kernel(int64_t rows, int64_t width, int64_t ld, float*
     const int64_t r = i / width;
     p[r * ld + (i - r * width)] = 0.f;
 }
+// (named for its two callers, dgn_node_ce_backward and dgn_masked_bce_backward: each loss's launch-count test looks for its own name)
+__global__ __launch_bounds__(256) void node_ce_bce_scale(int64_t n, int width, const float* __restrict__ g, int64_t ld_g,
+                                                         const float* __restrict__ g_loss, float* __restrict__ out, int64_t ld_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t r = i / width;
+    const int c = (int)(i - r * width);
+    out[r * ld_out + c] = g[r * ld_g + c] * *g_loss;
+}
 }  // namespace
 
 // rows x width floats := 0 (row stride ld) by a KERNEL: hipMemsetAsync nodes did not replay reliably under stream capture on this
@@ -39,6 +48,27 @@ int zero_rows_async(float* p, int64_t rows, int64_t width, int64_t ld, hipStream
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, rows, width, ld, p);
     DGN_HIP_CHECK(hipGetLastError());
     return DGN_OK;
+}
+
+int scale_rows_async(int64_t n_rows, int32_t width, const float* g, int64_t ld_g, const float* g_loss, float* out, int64_t ld_out, hipStream_t stream) {
+    const int64_t n = n_rows * width;
+    hipLaunchKernelGGL(node_ce_bce_scale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, width, g, ld_g, g_loss, out, ld_out);
+    DGN_HIP_CHECK(hipGetLastError());
+    return DGN_OK;
+}
+
+hipError_t allow_lds(LdsOptIn& done, int bytes, const void* const* kernels, int n_kernels) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0;
+    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
+    for (int i = 0; i < n_kernels; ++i) {
+        e = hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return e;
+    }
+    done.fetch_or(bit, std::memory_order_release);
+    return hipSuccess;
 }
 
 int hip_fail(hipError_t e, const char* what) {

@@ -179,11 +179,8 @@ int launch_backward_graph_cfg(const AggParams& p, hipStream_t stream) {
         tiles = (pairs + ppt - 1) / ppt;
         const size_t lds = lds_of(ppt);
         if (lds > 160 * 1024 || ((p.need & NEED_RECOMP) && !(p.aux && p.aux_rows))) return 1;
-        static bool attr = false;
-        if (!attr) {
-            DGN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&agg_bwd_graph<C, O>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr = true;
-        }
+        static LdsOptIn lds_ok{0};
+        DGN_HIP_CHECK(allow_lds(lds_ok, 160 * 1024, &agg_bwd_graph<C, O>));
         AggParams q = p;
         q.stage = nullptr; q.fresh = true; q.seg_add = false;
         hipLaunchKernelGGL((agg_bwd_graph<C, O>), dim3((unsigned)p.n_gblk, (unsigned)tiles), dim3(kGraphThreads), lds, stream, q, ppt);

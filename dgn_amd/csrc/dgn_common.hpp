@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "dgn_hip.h"
 
 namespace dgn {
@@ -23,6 +25,33 @@ enum Opt { OPT_BLK_LDS_KB, OPT_BLK_MIN_NODES, OPT_BWD_ROWS_PER_WAVE, OPT_TILE_GE
 int64_t option(Opt o);
 int hip_fail(hipError_t e, const char* what);
 int zero_rows_async(float* p, int64_t rows, int64_t width, int64_t ld, hipStream_t stream);   // capture-safe zero fill (dgn_abi.hip)
+// out[r, c] = g[r, c] * *g_loss over n_rows x width: the autograd backward of the losses that saved their gradient (dgn_abi.hip)
+int scale_rows_async(int64_t n_rows, int32_t width, const float* g, int64_t ld_g, const float* g_loss, float* out, int64_t ld_out, hipStream_t stream);
+
+// A kernel launched with more than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize, a per-DEVICE attribute of the
+// kernel (a second device in one process must not launch with the 64 KB default).  `done` is the launch site's function-local static:
+// the mask of the devices on which every kernel of the site has the attribute, published only after all of them were set -- whichever
+// thread comes first (setting it twice is harmless).  A device index beyond the mask's width sets the attribute on every call.
+using LdsOptIn = std::atomic<unsigned long long>;
+hipError_t allow_lds(LdsOptIn& done, int bytes, const void* const* kernels, int n_kernels);   // dgn_abi.hip
+template <class... K>
+inline hipError_t allow_lds(LdsOptIn& done, int bytes, K*... kernels) {
+    const void* const list[] = {reinterpret_cast<const void*>(kernels)...};
+    return allow_lds(done, bytes, list, (int)sizeof...(K));
+}
+
+// n items over at most max_groups workgroups of at least min_per items each: `per` items per workgroup, `groups` workgroups that have
+// some (0 for n = 0: the callers that launch one regardless clamp it), and `bound` >= groups, the count a workspace of one slot per
+// workgroup is sized by
+struct SlotSplit { int groups; int64_t per; int64_t bound; };
+inline SlotSplit slot_split(int64_t n, int64_t min_per, int64_t max_groups) {
+    int64_t g = (n + min_per - 1) / min_per;
+    if (g > max_groups) g = max_groups;
+    if (g < 1) g = 1;
+    int64_t per = (n + g - 1) / g;
+    if (per < 1) per = 1;
+    return {(int)((n + per - 1) / per), per, g};
+}
 // dgn_scale_combine_backward with the bias gradient WRITTEN instead of accumulated (set_bias != 0): the whole-layer calls (dgn_combine.hip)
 int scale_combine_backward_impl(int64_t n_nodes, int32_t T, int32_t S, int32_t fo, const float* g_y, int64_t ld_gy, const float* scale,
                                 const float* row_scale, float* g_z, float* g_bias, void* ws, size_t ws_bytes, const DgnBnGrad* bn,
@@ -184,6 +213,24 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
     return v;
+}
+
+__device__ __forceinline__ double shfl_xor_d(double v, int o) { return __shfl_xor(v, o, kWave); }
+// fp64 sum over a workgroup of WAVES waves as a fixed-shape tree: wave butterflies (offsets 1, 2, ... 32) with lane-ordered operands,
+// then the waves in order -- the same input gives the same bits.  s_red: WAVES doubles of LDS; the result on every thread.
+template <int WAVES>
+__device__ __forceinline__ double block_sum(double v, double* s_red) {
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const double a2 = shfl_xor_d(v, o);
+        v = (lane_id() & o) ? a2 + v : v + a2;
+    }
+    if (lane_id() == 0) s_red[threadIdx.x / kWave] = v;
+    __syncthreads();
+    double t = s_red[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) t += s_red[w];
+    return t;
 }
 
 }  // namespace dgn

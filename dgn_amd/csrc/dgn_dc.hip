@@ -49,12 +49,8 @@ WgPlan wgrad_plan(int64_t n_units, int k, int n) {
 
 template <int NTN, int KT>
 hipError_t launch_wgrad_t(const DcWgradParams& p, dim3 grid, size_t lds, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dc_wgrad<NTN, KT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static LdsOptIn lds_ok{0};
+    if (hipError_t e = allow_lds(lds_ok, 160 * 1024, &dc_wgrad<NTN, KT>)) return e;
     hipLaunchKernelGGL((dc_wgrad<NTN, KT>), grid, dim3(kWave * kWgWaves), lds, st, p);
     return hipGetLastError();
 }

@@ -27,7 +27,6 @@
 // order, the flag.  W = 32: 18 512 bytes, one wave-pair workgroup of 64 threads; W = 64: 69 456 bytes, 256 threads (dynamic LDS beyond 64 KB).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 
 #include "dgn_common.hpp"
@@ -251,17 +250,6 @@ __global__ __launch_bounds__(THREADS) void eig_small_kernel(Args a) {
     if (tid == 0) a.status[g] = sweeps;
 }
 
-template <class K>
-int allow_lds(K kernel, int bytes, std::atomic<unsigned long long>& done) {
-    int dev = 0;
-    DGN_HIP_CHECK(hipGetDevice(&dev));
-    const unsigned long long bit = dev < 64 ? 1ull << dev : 0;
-    if (bit && (done.load(std::memory_order_acquire) & bit)) return DGN_OK;
-    DGN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    done.fetch_or(bit, std::memory_order_release);
-    return DGN_OK;
-}
-
 }  // namespace eig_small
 }  // namespace dgn
 
@@ -284,8 +272,8 @@ extern "C" int dgn_eig_small(const DgnGraph* graph, const int64_t* graph_off, in
     if (n_graphs == 0) return DGN_OK;
     eig_small::Args a{graph->indptr, graph->src, graph->n_nodes, graph->n_edges, graph_off, k, norm, max_sweeps, vec, val, status};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    static std::atomic<unsigned long long> attr{0};
-    if (int rc = eig_small::allow_lds(&eig_small::eig_small_kernel<64, 256>, eig_small::Lds<64>::kBytes, attr)) return rc;
+    static LdsOptIn lds_ok{0};
+    DGN_HIP_CHECK(allow_lds(lds_ok, eig_small::Lds<64>::kBytes, &eig_small::eig_small_kernel<64, 256>));
     hipLaunchKernelGGL((eig_small::eig_small_kernel<32, 64>), dim3((unsigned)n_graphs), dim3(64), eig_small::Lds<32>::kBytes, s, a);
     DGN_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((eig_small::eig_small_kernel<64, 256>), dim3((unsigned)n_graphs), dim3(256), eig_small::Lds<64>::kBytes, s, a);

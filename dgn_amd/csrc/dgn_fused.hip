@@ -28,12 +28,8 @@ int n_cus() {
 
 template <class C, class O>
 int launch_fwd(const FusedParams& p, size_t lds, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        DGN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&layer_fwd_fused<C, O>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          160 * 1024));
-        attr = true;
-    }
+    static LdsOptIn lds_ok{0};
+    DGN_HIP_CHECK(allow_lds(lds_ok, 160 * 1024, &layer_fwd_fused<C, O>));
     const int per_cu = std::max(1, (int)(160 * 1024 / lds));                       // workgroups of one CU alternate between sweep and MFMA phases
     const unsigned grid = (unsigned)std::min<int64_t>(p.n_iters, (int64_t)n_cus() * per_cu);
     hipLaunchKernelGGL((layer_fwd_fused<C, O>), dim3(grid), dim3(kWave * kFusedWaves), lds, st, p);

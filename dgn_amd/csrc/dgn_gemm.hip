@@ -22,13 +22,8 @@ int n_cus() {
 template <int NT>
 hipError_t launch_gemm_nt(const GemmParams& p, dim3 grid, hipStream_t st, int wkn) {
     const size_t lds = (size_t)2 * NT * 16 * kKS * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ts_gemm<NT, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ts_gemm<NT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static LdsOptIn lds_ok{0};
+    if (hipError_t e = allow_lds(lds_ok, 160 * 1024, &ts_gemm<NT, 0>, &ts_gemm<NT, 1>)) return e;
     if (wkn) hipLaunchKernelGGL((ts_gemm<NT, 1>), grid, dim3(kWave * kWaves), lds, st, p);
     else hipLaunchKernelGGL((ts_gemm<NT, 0>), grid, dim3(kWave * kWaves), lds, st, p);
     return hipGetLastError();
@@ -46,12 +41,8 @@ hipError_t launch_gemm(int nt, const GemmParams& p, dim3 grid, hipStream_t st, i
 
 template <int KT>
 hipError_t launch_wgrad_kt(const WgradParams& p, dim3 grid, size_t lds, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ts_gemm_wgrad<KT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static LdsOptIn lds_ok{0};
+    if (hipError_t e = allow_lds(lds_ok, 160 * 1024, &ts_gemm_wgrad<KT>)) return e;
     hipLaunchKernelGGL((ts_gemm_wgrad<KT>), grid, dim3(kWave * kWgWaves), lds, st, p);
     return hipGetLastError();
 }
@@ -207,11 +198,8 @@ extern "C" int dgn_gemm_wgrad(int64_t n_rows, int32_t k, int32_t n, const float*
         p.G = g; p.ldg = ldg; p.X = x; p.ldx = ldx; p.part = static_cast<float*>(ws);
         const TwPlan t = tile_wgrad_plan(n_rows, p.kk, n);
         p.slots = t.slots; p.n_blocks = t.n_blocks; p.k_blocks = t.k_blocks; p.nb_tiles = t.nb_tiles; p.kb_tiles = t.kb_tiles;
-        static bool attr = false;
-        if (!attr) {
-            DGN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_wgrad), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr = true;
-        }
+        static LdsOptIn lds_ok{0};
+        DGN_HIP_CHECK(allow_lds(lds_ok, 160 * 1024, &tile_wgrad));
         hipLaunchKernelGGL(tile_wgrad, dim3(t.slots, t.n_blocks * t.k_blocks), dim3(kWave * kTwWaves), t.lds, st, p);
         const int64_t total = (int64_t)n * p.kk;
         hipLaunchKernelGGL(tile_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * 16), 0, st, n, k, p.kk, t.slots, t.k_blocks,

@@ -535,25 +535,16 @@ int bd_blocks(int T, int fi) {                       // 16-column blocks per tow
     return 0;
 }
 
-template <typename K>
-hipError_t bd_set_lds(K kernel) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
-}
-
 enum { kBdFwd = 0, kBdBwd = 1, kBdWg = 2, kBdBoth = 3 };
 
 template <int T, int FI>
 hipError_t bd_launch_one(int which, const BdParams& p, int threads, size_t lds, hipStream_t st) {
     static_assert(FI % 2 == 0 && FI % 16 != 0 && T * FI <= 16 * kMaxTiles, "even widths with room for the ones column");
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = bd_set_lds(&bd_forward<T, FI>);
-        if (e == hipSuccess) e = bd_set_lds(&bd_backward_input<T, FI>);
-        if (e == hipSuccess) e = bd_set_lds(&bd_wgrad<T, FI>);
-        if constexpr (FI <= 16) { if (e == hipSuccess) e = bd_set_lds(&bd_backward_both<T, FI>); }      // (two 16-column blocks per tower: 2 x the accumulators, spills)
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static LdsOptIn lds_ok{0};
+    hipError_t e;
+    if constexpr (FI <= 16) e = allow_lds(lds_ok, kLdsBudget, &bd_forward<T, FI>, &bd_backward_input<T, FI>, &bd_wgrad<T, FI>, &bd_backward_both<T, FI>);
+    else e = allow_lds(lds_ok, kLdsBudget, &bd_forward<T, FI>, &bd_backward_input<T, FI>, &bd_wgrad<T, FI>);      // (two 16-column blocks per tower: bd_backward_both would hold 2 x the accumulators, spills)
+    if (e != hipSuccess) return e;
     if (which == kBdFwd) hipLaunchKernelGGL((bd_forward<T, FI>), dim3(p.groups), dim3(threads), lds, st, p);
     else if (which == kBdBwd) hipLaunchKernelGGL((bd_backward_input<T, FI>), dim3(p.groups), dim3(threads), lds, st, p);
     else if (which == kBdBoth) {

@@ -846,24 +846,14 @@ hipError_t launch_linear_nkm(const LinParams& p, int threads, size_t lds, hipStr
     } else {
     if constexpr (linear_wreg_ok(NT, KB, MODE)) {
         if (p.wreg) {
-            static bool attr_w = false;
-            if (!attr_w) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ts_linear<NT, KB, MODE, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
-                if (e != hipSuccess) return e;
-                attr_w = true;
-            }
+            static LdsOptIn lds_ok_w{0};
+            if (hipError_t e = allow_lds(lds_ok_w, kLdsBudget, &ts_linear<NT, KB, MODE, true>)) return e;
             hipLaunchKernelGGL((ts_linear<NT, KB, MODE, true>), dim3(p.T * p.groups), dim3(threads), lds, st, p);
             return hipGetLastError();
         }
     }
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ts_linear<NT, KB, MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    static LdsOptIn lds_ok{0};
+    if (hipError_t e = allow_lds(lds_ok, kLdsBudget, &ts_linear<NT, KB, MODE>)) return e;
     hipLaunchKernelGGL((ts_linear<NT, KB, MODE>), dim3(p.T * p.groups), dim3(threads), lds, st, p);
     return hipGetLastError();
     }
@@ -873,13 +863,8 @@ hipError_t launch_wgrad_nke(const WgParams& p, size_t lds, hipStream_t st) {
     if constexpr (NT * KT > kMaxWgradTiles) {
         return hipErrorInvalidValue;
     } else {
-        static bool attr = false;
-        if (!attr) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ts_wgrad<NT, KT, EXPAND, GMASK>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
-            if (e != hipSuccess) return e;
-            attr = true;
-        }
+        static LdsOptIn lds_ok{0};
+        if (hipError_t e = allow_lds(lds_ok, kLdsBudget, &ts_wgrad<NT, KT, EXPAND, GMASK>)) return e;
         hipLaunchKernelGGL((ts_wgrad<NT, KT, EXPAND, GMASK>), dim3(p.T * p.groups), dim3(256), lds, st, p);
         return hipGetLastError();
     }

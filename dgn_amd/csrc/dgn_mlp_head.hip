@@ -27,8 +27,6 @@
 // lanes on consecutive addresses of a row: any 4-byte-aligned base and any row stride, no alignment to prove.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "dgn_common.hpp"
 
 namespace dgn {
@@ -97,14 +95,12 @@ inline bool dims_ok(int32_t n_lin, const int32_t* dims) {
 struct Split {
     int groups;                              // workgroups = workspace slots written
     int64_t tiles, per;                      // tiles in all, tiles per workgroup
+    int64_t bound;                           // upper bound of `groups`: the slots of the backward's workspace
 };
 inline Split split(int64_t n_rows) {
-    Split s{};
-    s.tiles = (n_rows + kTile - 1) / kTile;
-    int64_t g = s.tiles < kMaxGroups ? s.tiles : kMaxGroups;
-    s.per = g > 0 ? (s.tiles + g - 1) / g : 1;
-    s.groups = (int)((s.tiles + s.per - 1) / s.per);
-    return s;
+    const int64_t tiles = (n_rows + kTile - 1) / kTile;
+    const SlotSplit s = slot_split(tiles, 1, kMaxGroups);
+    return {s.groups, tiles, s.per, s.bound};
 }
 
 // the widths and the layout into LDS (no run-time index into the kernel arguments), then the parameters: W_l [d_l][d_{l-1}] as
@@ -293,18 +289,6 @@ __global__ __launch_bounds__(kThreads) void mlp_head_finalize(Params p, Grads g,
     }
 }
 
-// more than 64 KB of dynamic LDS needs the function attribute: once per device, whichever thread comes first (setting it twice is harmless)
-template <typename K>
-int allow_lds(K kernel, std::atomic<unsigned long long>& done) {
-    int dev = 0;
-    DGN_HIP_CHECK(hipGetDevice(&dev));
-    const unsigned long long bit = dev < 64 ? 1ull << dev : 0;
-    if (bit && (done.load(std::memory_order_acquire) & bit)) return DGN_OK;
-    DGN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-    done.fetch_or(bit, std::memory_order_release);
-    return DGN_OK;
-}
-
 // the checks the two entry points share; fills p
 inline int check_args(const char* who, int64_t n_rows, int32_t n_lin, const int32_t* dims, const float* const* w, const float* const* b, Params& p) {
     if (!dims_ok(n_lin, dims)) {
@@ -350,8 +334,8 @@ extern "C" int dgn_mlp_head_forward(int64_t n_rows, int32_t n_linears, const int
     if (n_rows == 0) return DGN_OK;
     if (!x || !y) { set_error("dgn_mlp_head_forward: null x / y"); return DGN_ERR_INVALID; }
     if (ld_x < dims[0] || ld_y < dims[n_linears]) { set_error("dgn_mlp_head_forward: row stride below the row's width"); return DGN_ERR_INVALID; }
-    static std::atomic<unsigned long long> attr{0};
-    if (int rc = mlp_head::allow_lds(&mlp_head::mlp_head_forward, attr)) return rc;
+    static LdsOptIn lds_ok{0};
+    DGN_HIP_CHECK(allow_lds(lds_ok, mlp_head::kLdsBytes, &mlp_head::mlp_head_forward));
     const mlp_head::Split s = mlp_head::split(n_rows);
     hipLaunchKernelGGL(mlp_head::mlp_head_forward, dim3((unsigned)s.groups), dim3(mlp_head::kThreads), mlp_head::lds_bytes(p),
                        static_cast<hipStream_t>(stream), n_rows, p, x, ld_x, y, ld_y, s.per, s.tiles);
@@ -361,9 +345,7 @@ extern "C" int dgn_mlp_head_forward(int64_t n_rows, int32_t n_linears, const int
 
 extern "C" size_t dgn_mlp_head_backward_workspace_bytes(int64_t n_rows, int32_t n_linears, const int32_t* dims) {
     if (n_rows < 0 || n_rows > INT32_MAX || !mlp_head::dims_ok(n_linears, dims)) return 0;
-    const int64_t tiles = (n_rows + mlp_head::kTile - 1) / mlp_head::kTile;
-    const int64_t slots = tiles < mlp_head::kMaxGroups ? (tiles > 0 ? tiles : 1) : mlp_head::kMaxGroups;    // the upper bound of `groups`
-    return (size_t)slots * (size_t)mlp_head::slot_floats(n_linears, dims) * sizeof(float);
+    return (size_t)mlp_head::split(n_rows).bound * (size_t)mlp_head::slot_floats(n_linears, dims) * sizeof(float);
 }
 
 extern "C" int dgn_mlp_head_backward(int64_t n_rows, int32_t n_linears, const int32_t* dims, const float* x, int64_t ld_x, const float* const* w,
@@ -396,8 +378,8 @@ extern "C" int dgn_mlp_head_backward(int64_t n_rows, int32_t n_linears, const in
         set_error("dgn_mlp_head_backward: workspace of %zu bytes (4-byte aligned) required, got %zu", need, ws_bytes);
         return DGN_ERR_INVALID;
     }
-    static std::atomic<unsigned long long> attr{0};
-    if (int rc = mlp_head::allow_lds(&mlp_head::mlp_head_backward, attr)) return rc;
+    static LdsOptIn lds_ok{0};
+    DGN_HIP_CHECK(allow_lds(lds_ok, mlp_head::kLdsBytes, &mlp_head::mlp_head_backward));
     const mlp_head::Split s = mlp_head::split(n_rows);
     hipLaunchKernelGGL(mlp_head::mlp_head_backward, dim3((unsigned)s.groups), block, mlp_head::lds_bytes(p), st, n_rows, p, x, ld_x, g_y, ld_gy, g_x,
                        ld_gx, static_cast<float*>(ws), s.per, s.tiles);

@@ -11,7 +11,7 @@
 //   emb_backward_fold     one thread per table element: the workgroups' partials added in workgroup order (fp64), written to table c
 //   bce_stats             one workgroup per contiguous element range: labelled count (integer) and the fp64 sum of the loss terms
 //   bce_rows              every workgroup folds the slots (count, loss), block 0 writes the loss; then the gradient of its range
-//   bce_scale             the autograd backward: g_saved * *g_loss
+//   (dgn::scale_rows_async, shared with the node loss: the autograd backward, g_saved * *g_loss)
 //
 // The tables' pointers travel in the kernel arguments (a struct by value): the parameters stay the separate nn.Embedding weights of the
 // state_dict and a captured graph holds their addresses like every other parameter's.  Indices outside a table are clamped (memory-safe).
@@ -64,15 +64,11 @@ inline bool emb_args_ok(int32_t n_cols, const int32_t* dims, int32_t F) {
 
 inline EmbLayout emb_layout(int64_t n_rows, int64_t total) {
     EmbLayout L{};
-    int64_t g = (n_rows + kMinRows - 1) / kMinRows;
-    if (g > kMaxGroups) g = kMaxGroups;
-    if (g < 1) g = 1;
-    L.per = (n_rows + g - 1) / g;
-    if (L.per < 1) L.per = 1;
-    L.groups = (int)((n_rows + L.per - 1) / L.per);
-    if (L.groups < 1) L.groups = 1;
+    const SlotSplit s = slot_split(n_rows, kMinRows, kMaxGroups);
+    L.groups = s.groups < 1 ? 1 : s.groups;
+    L.per = s.per;
     L.total = total;
-    L.bytes = (size_t)g * (size_t)total * sizeof(float);       // sized by the upper bound of `groups`
+    L.bytes = (size_t)s.bound * (size_t)total * sizeof(float);       // sized by the upper bound of `groups`
     return L;
 }
 
@@ -165,34 +161,13 @@ struct BceLayout {
 
 inline BceLayout bce_layout(int64_t n) {
     BceLayout L{};
-    int64_t g = (n + kBceMinElems - 1) / kBceMinElems;
-    if (g > kBceMaxGroups) g = kBceMaxGroups;
-    if (g < 1) g = 1;
-    L.per = (n + g - 1) / g;
-    if (L.per < 1) L.per = 1;
-    L.groups = (int)((n + L.per - 1) / L.per);
-    if (L.groups < 1) L.groups = 1;
+    const SlotSplit s = slot_split(n, kBceMinElems, kBceMaxGroups);
+    L.groups = s.groups < 1 ? 1 : s.groups;
+    L.per = s.per;
     L.lossp = 0;                                                // double [kBceMaxGroups]
     L.cnt = L.lossp + kBceMaxGroups * sizeof(double);           // int64  [kBceMaxGroups]
     L.bytes = L.cnt + kBceMaxGroups * sizeof(int64_t);
     return L;
-}
-
-__device__ __forceinline__ double shfl_xor_d(double v, int o) { return __shfl_xor(v, o, kWave); }
-
-// fixed-shape tree over the workgroup: wave butterflies with lane-ordered operands, then the waves in order; the result on every thread
-__device__ __forceinline__ double block_sum(double v, double* s_red) {
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const double a2 = shfl_xor_d(v, o);
-        v = (lane_id() & o) ? a2 + v : v + a2;
-    }
-    if (lane_id() == 0) s_red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    double t = s_red[0];
-#pragma unroll
-    for (int w = 1; w < kBceWaves; ++w) t += s_red[w];
-    return t;
 }
 
 __global__ __launch_bounds__(kBceThreads) void bce_stats(int64_t n, int T, const float* __restrict__ x, int64_t ld, const float* __restrict__ y,
@@ -216,7 +191,7 @@ __global__ __launch_bounds__(kBceThreads) void bce_stats(int64_t n, int T, const
         }
     }
     if (mine) atomicAdd(&s_cnt, mine);                           // (integer: exact in any order)
-    const double t = block_sum(acc, s_red);                      // (its barrier also orders the count)
+    const double t = block_sum<kBceWaves>(acc, s_red);                      // (its barrier also orders the count)
     if (tid == 0) { lossp[b] = t; cnt[b] = (int64_t)s_cnt; }
 }
 
@@ -230,7 +205,7 @@ __global__ __launch_bounds__(kBceThreads) void bce_rows(int64_t n, int T, const 
     if (tid == 0) s_cnt = 0ull;
     __syncthreads();
     if (tid < G && cnt[tid] > 0) atomicAdd(&s_cnt, (unsigned long long)cnt[tid]);      // G <= 256 = one slot per thread
-    const double total = block_sum(tid < G ? lossp[tid] : 0.0, s_red);
+    const double total = block_sum<kBceWaves>(tid < G ? lossp[tid] : 0.0, s_red);
     const int64_t labelled = (int64_t)s_cnt;
     // no labelled entry: 0 / 0 = nan, the mean over an empty selection (train_PCBA_graph_classification.py:32-33)
     if (b == 0 && tid == 0) *loss = (float)(total / (double)labelled);
@@ -249,15 +224,6 @@ __global__ __launch_bounds__(kBceThreads) void bce_rows(int64_t n, int T, const 
         }
         g[r * ld_g + c] = gv;
     }
-}
-
-__global__ __launch_bounds__(kBceThreads) void bce_scale(int64_t n, int T, const float* __restrict__ g, int64_t ld_g, const float* __restrict__ g_loss,
-                                                          float* __restrict__ out, int64_t ld_out) {
-    const int64_t i = (int64_t)blockIdx.x * kBceThreads + threadIdx.x;
-    if (i >= n) return;
-    const int64_t r = i / T;
-    const int c = (int)(i - r * T);
-    out[r * ld_out + c] = g[r * ld_g + c] * *g_loss;
 }
 
 }  // namespace mol_io
@@ -334,12 +300,8 @@ extern "C" int dgn_multi_embedding_backward(int64_t n_rows, int32_t n_cols, int3
         return DGN_ERR_INVALID;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    static bool attr = false;
-    if (!attr) {
-        DGN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mol_io::emb_backward_partial), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          mol_io::kLdsFloats * (int)sizeof(float)));
-        attr = true;
-    }
+    static LdsOptIn lds_ok{0};
+    DGN_HIP_CHECK(allow_lds(lds_ok, mol_io::kLdsFloats * (int)sizeof(float), &mol_io::emb_backward_partial));
     float* part = static_cast<float*>(ws);
     // (no row: one workgroup leaves a zero partial table, the fold writes the zero gradients)
     hipLaunchKernelGGL(mol_io::emb_backward_partial, dim3((unsigned)L.groups), dim3(mol_io::kBwdThreads), (size_t)total * sizeof(float), st, n_rows,
@@ -391,10 +353,6 @@ extern "C" int dgn_masked_bce_backward(int64_t n_rows, int32_t n_tasks, const fl
     if (n_rows == 0) return DGN_OK;
     if (!g_saved || !g_loss || !g_scores) { set_error("dgn_masked_bce_backward: null pointer"); return DGN_ERR_INVALID; }
     if (ld_g < T || ld_out < T) { set_error("dgn_masked_bce_backward: row stride below n_tasks"); return DGN_ERR_INVALID; }
-    const int64_t n = n_rows * T;
-    if (n > (int64_t)INT32_MAX * 64) { set_error("dgn_masked_bce_backward: n_rows x n_tasks beyond the grid range"); return DGN_ERR_INVALID; }
-    hipLaunchKernelGGL(mol_io::bce_scale, dim3((unsigned)((n + mol_io::kBceThreads - 1) / mol_io::kBceThreads)), dim3(mol_io::kBceThreads), 0,
-                       static_cast<hipStream_t>(stream), n, T, g_saved, ld_g, g_loss, g_scores, ld_out);
-    DGN_HIP_CHECK(hipGetLastError());
-    return DGN_OK;
+    if (n_rows * T > (int64_t)INT32_MAX * 64) { set_error("dgn_masked_bce_backward: n_rows x n_tasks beyond the grid range"); return DGN_ERR_INVALID; }
+    return scale_rows_async(n_rows, T, g_saved, ld_g, g_loss, g_scores, ld_out, static_cast<hipStream_t>(stream));
 }

@@ -37,13 +37,10 @@ struct Layout {
 
 inline Layout layout(int64_t n_rows, int32_t C) {
     Layout L{};
-    int64_t g = (n_rows + kMinRows - 1) / kMinRows;
-    if (g > kMaxGroups) g = kMaxGroups;
-    if (g < 1) g = 1;
-    L.per = (n_rows + g - 1) / g;
-    if (L.per < 1) L.per = 1;
-    L.groups = (int)((n_rows + L.per - 1) / L.per);
-    const size_t G = (size_t)(g);    // sized by the upper bound of `groups`
+    const SlotSplit s = slot_split(n_rows, kMinRows, kMaxGroups);
+    L.groups = s.groups;
+    L.per = s.per;
+    const size_t G = (size_t)s.bound;    // sized by the upper bound of `groups`
     L.cols = 0;                                              // double [G][32]
     L.lossp = L.cols + G * kMaxC * sizeof(double);           // double [G]
     L.cnt = L.lossp + G * sizeof(double);                    // int    [G][32]
@@ -52,8 +49,6 @@ inline Layout layout(int64_t n_rows, int32_t C) {
     L.bytes = L.cm + G * (size_t)C * C * sizeof(int);
     return L;
 }
-
-__device__ __forceinline__ double shfl_xor_d(double v, int o) { return __shfl_xor(v, o, kWave); }
 
 // (m, s) := log-sum-exp pair of the union; s in units of exp(m)
 __device__ __forceinline__ void lse_merge(float& m, double& s, float m2, double s2) {
@@ -199,21 +194,6 @@ __device__ __forceinline__ void fold_slots(int C, int G, const int* __restrict__
     __syncthreads();
 }
 
-// fixed-shape tree over the workgroup: wave butterflies with lane-ordered operands, then the waves in order; the result on thread 0
-__device__ __forceinline__ double block_sum(double v, double* s_red) {
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const double a2 = shfl_xor_d(v, o);
-        v = (lane_id() & o) ? a2 + v : v + a2;
-    }
-    if (lane_id() == 0) s_red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    double t = s_red[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) t += s_red[w];
-    return t;
-}
-
 template <int CP>
 __global__ __launch_bounds__(kThreads) void node_ce_rows(int64_t N, int C, const float* __restrict__ scores, int64_t ld,
                                                           const int64_t* __restrict__ labels, int64_t per, int G, const int* __restrict__ cnt,
@@ -289,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void node_ce_rows(int64_t N, int C, const
             atomicAdd(&s_cm[y * C + best], 1);
         }
     }
-    const double t = block_sum(acc, s_red);
+    const double t = block_sum<kWaves>(acc, s_red);
     if (tid == 0) lossp[b] = t;
     if (cmp)
         for (int i = tid; i < C * C; i += kThreads) cmp[(int64_t)b * C * C + i] = s_cm[i];
@@ -302,7 +282,7 @@ __global__ __launch_bounds__(kThreads) void node_ce_finish(int C, int G, const i
     __shared__ double s_red[kWaves];
     const int tid = threadIdx.x;
     fold_slots(C, G, cnt, nullptr, nullptr, s_count, nullptr);
-    const double total = block_sum(tid < G ? lossp[tid] : 0.0, s_red);           // G <= 256 = one slot per thread
+    const double total = block_sum<kWaves>(tid < G ? lossp[tid] : 0.0, s_red);           // G <= 256 = one slot per thread
     if (tid == 0) {
         int64_t V = 0;
         for (int c = 0; c < C; ++c) V += s_count[c];
@@ -322,15 +302,6 @@ __global__ __launch_bounds__(kThreads) void node_ce_finish(int C, int G, const i
             for (int s = 0; s < G; ++s) t += cmp[(int64_t)s * C * C + i];
             confusion[i] = t;
         }
-}
-
-__global__ __launch_bounds__(kThreads) void node_ce_scale(int64_t n_rows, int C, const float* __restrict__ g, int64_t ld_g,
-                                                           const float* __restrict__ g_loss, float* __restrict__ out, int64_t ld_out) {
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n_rows * C) return;
-    const int64_t r = i / C;
-    const int c = (int)(i - r * C);
-    out[r * ld_out + c] = g[r * ld_g + c] * *g_loss;
 }
 
 }  // namespace node_ce
@@ -398,9 +369,5 @@ extern "C" int dgn_node_ce_backward(int64_t n_rows, int32_t n_classes, const flo
     if (n_rows == 0) return DGN_OK;
     if (!g_saved || !g_loss || !g_scores) { set_error("dgn_node_ce_backward: null pointer"); return DGN_ERR_INVALID; }
     if (ld_g < C || ld_out < C) { set_error("dgn_node_ce_backward: row stride below n_classes"); return DGN_ERR_INVALID; }
-    const int64_t n = n_rows * C;
-    hipLaunchKernelGGL(node_ce::node_ce_scale, dim3((unsigned)((n + node_ce::kThreads - 1) / node_ce::kThreads)), dim3(node_ce::kThreads), 0,
-                       static_cast<hipStream_t>(stream), n_rows, C, g_saved, ld_g, g_loss, g_scores, ld_out);
-    DGN_HIP_CHECK(hipGetLastError());
-    return DGN_OK;
+    return scale_rows_async(n_rows, C, g_saved, ld_g, g_loss, g_scores, ld_out, static_cast<hipStream_t>(stream));
 }

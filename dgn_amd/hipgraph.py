@@ -112,7 +112,52 @@ def rewrap_parameters(module: torch.nn.Module) -> None:
         m.__dict__.pop("_opmap", None)
 
 
-class CapturedNetStep:
+class _CapturedStep:
+    """What the captured steps share: the device, the refusal of nets the static buffers cannot hold, the ``PaddedBatch`` with the graph
+    norm buffer, the loss scalar, the optimizer and the capture / replay of ``_step`` (the subclass's: one whole training step that reads
+    the static buffers and leaves the loss in ``self.loss``)."""
+
+    _REFUSED = ()      # (test of the net, the ValueError's text) pairs, in the order they are checked
+
+    def __init__(self, net, n_cap: int, e_cap: int, eig_dim: int, device=None):
+        dev = torch.device(device if device is not None else next(net.parameters()).device)
+        for refused, why in self._REFUSED:
+            if refused(net):
+                raise ValueError(why)
+        self.net, self.device = net, dev
+        self.pb = PaddedBatch(n_cap, e_cap, dev, eig_dim)
+        self.snorm = self.pb.add_node_tensor("snorm", 1)
+        self.loss = torch.zeros((), device=dev)
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+
+    def _set_optimizer(self, optimizer, lr: float) -> None:
+        """The last act of a constructor (a refused construction leaves the net's Parameter objects alone)."""
+        if optimizer is None:
+            rewrap_parameters(self.net)
+            try:                   # one multi-tensor kernel for all ~120 parameter tensors (the per-tensor form is ~1 ms of tiny kernels per step)
+                optimizer = torch.optim.Adam(self.net.parameters(), lr=lr, capturable=True, fused=True)
+            except Exception:
+                optimizer = torch.optim.Adam(self.net.parameters(), lr=lr, capturable=True)
+        self.opt = optimizer
+
+    def capture(self, warmup: int = 3) -> None:
+        """Capture the step on the batch currently loaded (the warm-up steps DO update the parameters)."""
+        self.graph = capture(self._step, warmup=warmup)
+
+    def step(self) -> torch.Tensor:
+        """One training step on the loaded batch; returns the (device) loss of that step."""
+        if self.graph is None:
+            self._step()
+        else:
+            self.graph.replay()
+        return self.loss
+
+
+_HAS_EDGE_FEAT = lambda net: getattr(net, "edge_feat", False)
+_HAS_POS_ENC = lambda net: getattr(net, "pos_enc_dim", 0) > 0
+
+
+class CapturedNetStep(_CapturedStep):
     """One captured HIP graph for the whole training step of a net around the layers (``dgn_amd.nets.DGNNet``: embedding, L layers,
     readout, MLP, L1 loss, backward, Adam) at a fixed capacity: ``load(batch)`` writes the batch into static buffers (graph rebuilt in
     place, atoms / graph norm / targets / the readout's graph -> nodes CSR copied), ``step()`` is one graph launch.
@@ -130,6 +175,8 @@ class CapturedNetStep:
     training steps on the default stream before a capture are otherwise fatal) and a capturable Adam is built on the new ones."""
 
     PAD_ROWS = 16      # readout rows behind the real graphs that share the padding nodes
+    _REFUSED = ((_HAS_EDGE_FEAT, "CapturedNetStep: nets with edge_feat=True are not supported (the captured step has no static bond-type "
+                                 "buffer); run them eagerly or build the net with edge_feat=False"),)
 
     def __init__(self, net, n_cap: int, e_cap: int, g_cap: int, eig_dim: int, lr: float = 1e-3, optimizer=None, device=None,
                  max_graph_nodes: Optional[int] = None, max_graph_edges: Optional[int] = None):
@@ -137,24 +184,18 @@ class CapturedNetStep:
         gets a static block table (``DGNGraph.set_block_capacity``) and the captured step runs its layers on the graph-block route -- five
         launches per layer and step instead of ~28."""
         from .graph import DGNGraph
-        dev = torch.device(device if device is not None else next(net.parameters()).device)
-        if getattr(net, "edge_feat", False):
-            raise ValueError("CapturedNetStep: nets with edge_feat=True are not supported (the captured step has no static bond-type "
-                             "buffer); run them eagerly or build the net with edge_feat=False")
+        super().__init__(net, n_cap, e_cap, eig_dim, device)
+        dev = self.device
         # graph rows of the readout: g_cap - 1 real graphs at most, then PAD_ROWS rows that share the padding nodes (ONE padding row was a
         # single wave walking ~10 % of the batch's nodes in sequence: 40 us per direction of a 0.77 ms step)
         self.g_cap = int(g_cap)
-        self.net, self.device = net, dev
         g_cap = self.g_rows = self.g_cap - 1 + self.PAD_ROWS
-        self.pb = PaddedBatch(n_cap, e_cap, dev, eig_dim)
         if max_graph_nodes and max_graph_edges:
             self.pb.graph.set_block_capacity(g_cap, max_graph_nodes, max_graph_edges)
         self.atoms = torch.zeros(n_cap, dtype=torch.int64, device=dev)
-        self.snorm = self.pb.add_node_tensor("snorm", 1)
         self.targets = torch.zeros(g_cap, 1, device=dev)
         self.gmask = torch.zeros(g_cap, 1, device=dev)
         self.n_graphs = torch.ones(1, device=dev)
-        self.loss = torch.zeros((), device=dev)
         self._h_sizes = torch.zeros(g_cap, dtype=torch.int64).pin_memory()
         self._d_sizes = torch.zeros(g_cap, dtype=torch.int64, device=dev)
         self._g_ids = torch.arange(g_cap, device=dev).unsqueeze(1)
@@ -173,14 +214,7 @@ class CapturedNetStep:
         rg.sizes = rg.in_degree
         self.rg = rg
         self.pb.graph._dgn_readout = rg
-        if optimizer is None:
-            rewrap_parameters(net)
-            try:                   # one multi-tensor kernel for all ~120 parameter tensors (the per-tensor form is ~1 ms of tiny kernels per step)
-                optimizer = torch.optim.Adam(net.parameters(), lr=lr, capturable=True, fused=True)
-            except Exception:
-                optimizer = torch.optim.Adam(net.parameters(), lr=lr, capturable=True)
-        self.opt = optimizer
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._set_optimizer(optimizer, lr)
 
     @torch.no_grad()
     def load(self, src, dst, num_nodes: int, eig, atoms, snorm, sizes, targets) -> None:
@@ -230,18 +264,6 @@ class CapturedNetStep:
         """The net's loss over the real graph rows (mean absolute error; the rows behind the batch are masked)."""
         return ((scores - self.targets).abs() * self.gmask).sum() / self.n_graphs
 
-    def capture(self, warmup: int = 3) -> None:
-        """Capture the step on the batch currently loaded (the warm-up steps DO update the parameters)."""
-        self.graph = capture(self._step, warmup=warmup)
-
-    def step(self) -> torch.Tensor:
-        """One training step on the loaded batch; returns the (device) loss of that step."""
-        if self.graph is None:
-            self._step()
-        else:
-            self.graph.replay()
-        return self.loss
-
 
 class CapturedMolStep(CapturedNetStep):
     """``CapturedNetStep`` for the OGB molecule nets (``dgn_amd.nets.DGNHIVNet`` / ``DGNPCBANet``: AtomEncoder, L layers, readout, MLP,
@@ -254,12 +276,12 @@ class CapturedMolStep(CapturedNetStep):
     ``virtual_node`` (the VirtualNode layers' BatchNorm runs over the graph rows and would count the padding rows in its statistics, and
     their broadcast to the nodes has a data-dependent size): run those nets eagerly."""
 
+    _REFUSED = ((_HAS_POS_ENC, "CapturedMolStep: nets with pos_enc_dim > 0 are not supported (no static positional-encoding buffer)"),
+                (lambda net: getattr(net, "virtual_node_layers", None) is not None,
+                 "CapturedMolStep: nets with virtual_node are not supported (the VirtualNode layers' BatchNorm over the graph rows "
+                 "would count the padding rows); run them eagerly or build the net with virtual_node=None")) + CapturedNetStep._REFUSED
+
     def __init__(self, net, n_cap: int, e_cap: int, g_cap: int, eig_dim: int, **kwargs):
-        if getattr(net, "pos_enc_dim", 0) > 0:
-            raise ValueError("CapturedMolStep: nets with pos_enc_dim > 0 are not supported (no static positional-encoding buffer)")
-        if getattr(net, "virtual_node_layers", None) is not None:
-            raise ValueError("CapturedMolStep: nets with virtual_node are not supported (the VirtualNode layers' BatchNorm over the graph rows "
-                             "would count the padding rows); run them eagerly or build the net with virtual_node=None")
         super().__init__(net, n_cap, e_cap, g_cap, eig_dim, **kwargs)
         n_cols = len(net.embedding_h.dims)
         self.atoms = torch.zeros(self.pb.n_cap, n_cols, dtype=torch.int64, device=self.device)
@@ -277,7 +299,7 @@ class CapturedMolStep(CapturedNetStep):
         return self.net.loss(scores, self.targets)
 
 
-class CapturedNodeStep:
+class CapturedNodeStep(_CapturedStep):
     """One captured HIP graph for the whole training step of the node-classification net (``dgn_amd.nets.DGNNodeNet``: embedding, L
     layers, per-node MLP, batch-balanced cross-entropy with the confusion matrix of ``accuracy_sbm``, backward, Adam) at a fixed capacity:
     ``load(batch)`` writes the batch into static buffers, ``step()`` is one graph launch and returns ``(loss, confusion)`` device tensors.
@@ -288,28 +310,17 @@ class CapturedNodeStep:
     ``optimizer``: as for ``CapturedNetStep`` (capturable, built on parameters that never took part in a default-stream autograd pass);
     by default the net's Parameter objects are re-created (``rewrap_parameters``) and a capturable Adam is built on them."""
 
+    _REFUSED = ((_HAS_EDGE_FEAT, "CapturedNodeStep: nets with edge_feat=True are not supported (no static edge-feature buffer)"),
+                (_HAS_POS_ENC, "CapturedNodeStep: nets with pos_enc_dim > 0 are not supported (no static positional-encoding buffer)"))
+
     def __init__(self, net, n_cap: int, e_cap: int, eig_dim: int, lr: float = 1e-3, optimizer=None, device=None):
-        dev = torch.device(device if device is not None else next(net.parameters()).device)
-        if getattr(net, "edge_feat", False):
-            raise ValueError("CapturedNodeStep: nets with edge_feat=True are not supported (no static edge-feature buffer)")
-        if getattr(net, "pos_enc_dim", 0) > 0:
-            raise ValueError("CapturedNodeStep: nets with pos_enc_dim > 0 are not supported (no static positional-encoding buffer)")
-        self.net, self.device = net, dev
+        super().__init__(net, n_cap, e_cap, eig_dim, device)
+        dev = self.device
         self.n_classes = int(net.n_classes)
-        self.pb = PaddedBatch(n_cap, e_cap, dev, eig_dim)
         self.feats = torch.zeros(n_cap, dtype=torch.int64, device=dev)
-        self.snorm = self.pb.add_node_tensor("snorm", 1)
         self.labels = torch.full((n_cap,), -1, dtype=torch.int64, device=dev)
-        self.loss = torch.zeros((), device=dev)
         self.confusion = torch.zeros(self.n_classes, self.n_classes, dtype=torch.int64, device=dev)
-        if optimizer is None:
-            rewrap_parameters(net)
-            try:
-                optimizer = torch.optim.Adam(net.parameters(), lr=lr, capturable=True, fused=True)
-            except Exception:
-                optimizer = torch.optim.Adam(net.parameters(), lr=lr, capturable=True)
-        self.opt = optimizer
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._set_optimizer(optimizer, lr)
 
     @torch.no_grad()
     def load(self, src, dst, num_nodes: int, eig, feats, snorm, labels, sizes=None) -> None:
@@ -332,14 +343,7 @@ class CapturedNodeStep:
         self.confusion.copy_(cm)
         del scores, loss, cm
 
-    def capture(self, warmup: int = 3) -> None:
-        """Capture the step on the batch currently loaded (the warm-up steps DO update the parameters)."""
-        self.graph = capture(self._step, warmup=warmup)
-
     def step(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """One training step on the loaded batch; returns the (device) loss and confusion matrix of that step."""
-        if self.graph is None:
-            self._step()
-        else:
-            self.graph.replay()
+        super().step()
         return self.loss, self.confusion

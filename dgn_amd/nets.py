@@ -69,11 +69,23 @@ def small_table_embedding(emb: nn.Embedding, idx: torch.Tensor) -> torch.Tensor:
     return emb(idx)
 
 
+def _dgn_layers(p: dict, towers=None) -> nn.ModuleList:
+    """The nets' layer stack from the constructor dictionary: ``L - 1`` layers ``hidden_dim -> hidden_dim`` and one to ``out_dim``, created
+    in that order (the order of the initialisation's RNG draws); ``towers=None`` leaves the layer factory's default."""
+    hidden = p["hidden_dim"]
+    extra = {} if towers is None else {"towers": towers}
+    make = lambda o: DGNLayer(in_dim=hidden, out_dim=o, dropout=p["dropout"], graph_norm=p["graph_norm"], batch_norm=p["batch_norm"],
+                              residual=p["residual"], aggregators=p["aggregators"], scalers=p["scalers"], avg_d=p["avg_d"],
+                              type_net=p["type_net"], edge_features=p["edge_feat"], edge_dim=p["edge_dim"],
+                              pretrans_layers=p["pretrans_layers"], posttrans_layers=p["posttrans_layers"], **extra).model
+    return nn.ModuleList([make(hidden) for _ in range(p["L"] - 1)] + [make(p["out_dim"])])
+
+
 class DGNNet(nn.Module):
     def __init__(self, net_params: dict):
         super().__init__()
         p = net_params
-        hidden, out_dim, n_layers = p["hidden_dim"], p["out_dim"], p["L"]
+        hidden, out_dim = p["hidden_dim"], p["out_dim"]
         self.type_net, self.pos_enc_dim, self.readout = p["type_net"], p["pos_enc_dim"], p["readout"]
         self.edge_feat, self.device = p["edge_feat"], p["device"]
         self.in_feat_dropout = nn.Dropout(p["in_feat_dropout"])
@@ -82,11 +94,7 @@ class DGNNet(nn.Module):
             self.embedding_pos_enc = nn.Linear(self.pos_enc_dim, hidden)
         if self.edge_feat:
             self.embedding_e = nn.Embedding(p["num_bond_type"], p["edge_dim"])
-        make = lambda o: DGNLayer(in_dim=hidden, out_dim=o, dropout=p["dropout"], graph_norm=p["graph_norm"], batch_norm=p["batch_norm"],
-                                  residual=p["residual"], aggregators=p["aggregators"], scalers=p["scalers"], avg_d=p["avg_d"],
-                                  type_net=self.type_net, edge_features=self.edge_feat, edge_dim=p["edge_dim"],
-                                  pretrans_layers=p["pretrans_layers"], posttrans_layers=p["posttrans_layers"]).model
-        self.layers = nn.ModuleList([make(hidden) for _ in range(n_layers - 1)] + [make(out_dim)])
+        self.layers = _dgn_layers(p)
         directional = self.readout in ("directional", "directional_abs")
         self.MLP_layer = MLPReadout(2 * out_dim if directional else out_dim, 1)
 
@@ -118,18 +126,14 @@ class DGNNodeNet(nn.Module):
     def __init__(self, net_params: dict):
         super().__init__()
         p = net_params
-        hidden, out_dim, n_layers = p["hidden_dim"], p["out_dim"], p["L"]
+        hidden, out_dim = p["hidden_dim"], p["out_dim"]
         self.type_net, self.pos_enc_dim, self.readout = p["type_net"], p["pos_enc_dim"], p["readout"]
         self.edge_feat, self.device, self.n_classes = p["edge_feat"], p["device"], p["n_classes"]
         if self.pos_enc_dim > 0:
             self.embedding_pos_enc = nn.Linear(self.pos_enc_dim, hidden)
         self.embedding_h = nn.Embedding(p["in_dim"], hidden)
         self.in_feat_dropout = nn.Dropout(p["in_feat_dropout"])
-        make = lambda o: DGNLayer(in_dim=hidden, out_dim=o, dropout=p["dropout"], graph_norm=p["graph_norm"], batch_norm=p["batch_norm"],
-                                  residual=p["residual"], aggregators=p["aggregators"], scalers=p["scalers"], avg_d=p["avg_d"],
-                                  type_net=self.type_net, edge_features=self.edge_feat, edge_dim=p["edge_dim"],
-                                  pretrans_layers=p["pretrans_layers"], posttrans_layers=p["posttrans_layers"]).model
-        self.layers = nn.ModuleList([make(hidden) for _ in range(n_layers - 1)] + [make(out_dim)])
+        self.layers = _dgn_layers(p)
         self.MLP_layer = MLPReadout(out_dim, self.n_classes)
 
     def forward(self, g, h, e, snorm_n, snorm_e=None):
@@ -269,12 +273,7 @@ class _DGNMolNet(nn.Module):
         self.embedding_h = AtomEncoder(emb_dim=hidden)
         if self.edge_feat:
             self.embedding_e = BondEncoder(emb_dim=p["edge_dim"])
-        extra = {} if towers is None else {"towers": towers}
-        make = lambda o: DGNLayer(in_dim=hidden, out_dim=o, dropout=p["dropout"], graph_norm=p["graph_norm"], batch_norm=p["batch_norm"],
-                                  residual=p["residual"], aggregators=p["aggregators"], scalers=p["scalers"], avg_d=p["avg_d"],
-                                  type_net=self.type_net, edge_features=self.edge_feat, edge_dim=p["edge_dim"],
-                                  pretrans_layers=p["pretrans_layers"], posttrans_layers=p["posttrans_layers"], **extra).model
-        self.layers = nn.ModuleList([make(hidden) for _ in range(n_layers - 1)] + [make(out_dim)])
+        self.layers = _dgn_layers(p, towers)
         self.MLP_layer = MLPReadout(out_dim, n_tasks, decreasing_dim=decreasing_dim)
         self.virtual_node_layers = None
         if virtual_node is not None and virtual_node.lower() != "none":

@@ -122,6 +122,31 @@ def test_embedding_backward_through_a_strided_index_view_and_two_runs_at_the_lar
         assert a[c].numpy().tobytes() == b[c].numpy().tobytes()
 
 
+def test_embedding_backward_above_64_kb_of_lds_on_a_second_device_of_the_process():
+    """173 x 96 floats = 66 432 bytes of dynamic LDS, the smallest OGB-atom case above the 64 KB a kernel may use without its per-device
+    attribute; 65 rows = two partial-table slots.  The same call on cuda:0 and then on cuda:1 of one process: bit-equal outputs and
+    gradients (both deterministic), each against the torch composition as in the backward test above."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices in one process")
+    dims, F, N = TABLES[9], 96, 65
+    weights = _tables(dims, F, seed=12)
+    idx = _indices(dims, N, seed=13)
+    cot = torch.randn(N, F, generator=torch.Generator().manual_seed(14))
+    ref = _composition(weights, idx)
+    r32, r64 = _composition_grads(weights, idx, cot, torch.float32), _composition_grads(weights, idx, cot, torch.float64)
+    runs = []
+    for d in (0, 1):
+        with torch.cuda.device(d):                                         # (torch.device("cuda") in _fused = the current device)
+            out, grads = _fused(weights, idx.to(torch.device("cuda", d)), cot)
+        assert out.numpy().tobytes() == ref.numpy().tobytes(), d
+        for c in range(len(dims)):
+            parity_util.check_reduced(grads[c], r32[c], r64[c], f"multi_embedding N={N} F={F} C=9 cuda:{d} table {c}")
+        runs.append((out, grads))
+    assert runs[0][0].numpy().tobytes() == runs[1][0].numpy().tobytes()
+    for a, b in zip(runs[0][1], runs[1][1]):
+        assert a.numpy().tobytes() == b.numpy().tobytes()
+
+
 def test_embedding_out_of_range_indices_are_clamped_and_validate_raises():
     from dgn_amd import ops
     dev = torch.device("cuda")
