@@ -96,6 +96,9 @@ const OptDef kOpts[OPT_COUNT] = {
     {"lin_wreg", "DGN_LIN_WREG", 3, false},                     // streaming posttrans products up to 18 tiles with the weights register-resident, 12 waves per CU: bit 0 the combine-epilogue product, bit 1 the expanded-operand product (0: weights re-read from LDS per strip, 16 waves)
     {"bd_bwd_fused", "DGN_BD_BWD_FUSED", 1, false},             // towers layer backward: the block-diagonal pretrans product's input gradient and weight gradient in one pass over d(P|Q) (0: two kernels)
     {"bn_stats_fused", "DGN_BN_STATS_FUSED", 1, false},         // towers layer forward: BatchNorm's column sums ride in the posttrans product's combine epilogue (fp64 LDS cells; 0: bn_stats, a pass of its own over y0)
+    {"ew_big_min", "DGN_EW_BIG_MIN", 1 << 19, false},           // edge weights: batches from this many rows on pick their row classes by ballot (64 candidate rows per wave)
+    {"ew_separate", "DGN_EW_SEPARATE", 0, true},                // edge weights: one launch per row class on small batches too (0: the three classes in ew_rows_small)
+    {"ew_no_flat8", "DGN_EW_NO_FLAT8", 0, true},                // edge weights: batches whose largest in-degree is 5 .. 8 take the general classes (0: ew_rows_flat8)
 };
 std::atomic<int64_t> g_opt[OPT_COUNT];
 std::once_flag g_opt_once;

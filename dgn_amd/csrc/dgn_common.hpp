@@ -21,7 +21,7 @@ void set_error(const char* fmt, ...);
 // Library options (dgn_set_option / dgn_get_option of the C ABI): process-wide switches the tests and experiments flip.  Each is
 // initialised ONCE from its environment variable when the library first looks (no getenv on any launch path) and changed only through
 // the setter.  -1 = "auto" where the library has a rule of its own.
-enum Opt { OPT_BLK_LDS_KB, OPT_BLK_MIN_NODES, OPT_BWD_ROWS_PER_WAVE, OPT_TILE_GEMM, OPT_TILE_WGRAD, OPT_NO_ZMASK, OPT_LINEAR_SMALL_MIN_WAVES, OPT_GRAPH_BWD_TILES, OPT_ODD_DIRECT, OPT_BN_FROM_WGRAD, OPT_MIX_BWD_FUSED, OPT_BLK_LDS_PAD_KB, OPT_LIN_WREG, OPT_BD_BWD_FUSED, OPT_BN_STATS_FUSED, OPT_COUNT };
+enum Opt { OPT_BLK_LDS_KB, OPT_BLK_MIN_NODES, OPT_BWD_ROWS_PER_WAVE, OPT_TILE_GEMM, OPT_TILE_WGRAD, OPT_NO_ZMASK, OPT_LINEAR_SMALL_MIN_WAVES, OPT_GRAPH_BWD_TILES, OPT_ODD_DIRECT, OPT_BN_FROM_WGRAD, OPT_MIX_BWD_FUSED, OPT_BLK_LDS_PAD_KB, OPT_LIN_WREG, OPT_BD_BWD_FUSED, OPT_BN_STATS_FUSED, OPT_EW_BIG_MIN, OPT_EW_SEPARATE, OPT_EW_NO_FLAT8, OPT_COUNT };
 int64_t option(Opt o);
 int hip_fail(hipError_t e, const char* what);
 int zero_rows_async(float* p, int64_t rows, int64_t width, int64_t ld, hipStream_t stream);   // capture-safe zero fill (dgn_abi.hip)

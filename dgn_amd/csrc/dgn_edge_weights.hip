@@ -518,10 +518,10 @@ extern "C" int dgn_edge_weights(const DgnGraph* g, const float* eig, const float
     }
     // (round 6: 2^20 -> 2^19 rows.  Below it the three classes are one launch of N / 64 + N / 4 + N one-wave workgroups, most of which
     //  leave at once: at 960 k k-NN rows (c3_mega) the dispatcher alone is 0.26 ms of a 0.383-ms launch; the ballot path takes 0.139)
-    static const int64_t big_min = getenv("DGN_EW_BIG_MIN") ? atoll(getenv("DGN_EW_BIG_MIN")) : (1 << 19);
+    const int64_t big_min = option(OPT_EW_BIG_MIN);
     const bool big = p.n_nodes >= big_min;         // row classes by ballot (64 candidate rows per wave) vs a wave / 16 lanes per row
-    static const bool no_merge = getenv("DGN_EW_SEPARATE") != nullptr;
-    static const bool no_flat8 = getenv("DGN_EW_NO_FLAT8") != nullptr;
+    const bool no_merge = option(OPT_EW_SEPARATE) != 0;
+    const bool no_flat8 = option(OPT_EW_NO_FLAT8) != 0;
     if (!no_flat8 && g->max_in_degree > kFlatMax && g->max_in_degree <= 8) {      // every row at most 8 slots: a thread per row, one launch
         hipLaunchKernelGGL(ew_rows_flat8, dim3((unsigned)((p.n_nodes + 255) / 256)), dim3(256), 0, stream, p);
     } else if (!big && !no_merge && (g->max_in_degree == 0 || g->max_in_degree > kFlatMax)) {

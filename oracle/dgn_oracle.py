@@ -112,13 +112,65 @@ def agg_dir_dx(m, eig_s, eig_d, x, k):
 
 def agg_dir_dx_balanced(m, eig_s, eig_d, x, k):
     """aggregators.py:62-71: forward and backward fields normalised separately, averaged."""
+    w = _balanced_pair(eig_s, eig_d, k)
+    return ((m * w).sum(dim=1) - w.sum(dim=1) * x).abs()
+
+
+def _balanced_pair(eig_s, eig_d, k):
+    """(relu(d) / (sum relu(d) + EPS) + relu(-d) / (sum relu(-d) + EPS)) / 2, shape [n, D, 1]  (aggregators.py:63-69)."""
     d = _delta(eig_s, eig_d, k)
     fwd = torch.relu(d)
     bwd = torch.relu(-d)
     fwd = (fwd / (fwd.abs().sum(dim=1, keepdim=True) + EPS)).unsqueeze(-1)
     bwd = (bwd / (bwd.abs().sum(dim=1, keepdim=True) + EPS)).unsqueeze(-1)
-    w = (fwd + bwd) / 2
-    return ((m * w).sum(dim=1) - w.sum(dim=1) * x).abs()
+    return (fwd + bwd) / 2
+
+
+# ----------------------------------------------------------------------------
+# the per-edge directional weights themselves (what the aggregators above multiply the mailbox by)
+# ----------------------------------------------------------------------------
+
+W_ABSNORM, W_BALANCED, W_SOFTMAX = range(3)      # channel kinds of dgn_amd/spec.py (include/dgn_hip.h: DGN_W_*)
+
+
+def edge_weights_ref(indptr, src, eig, channels, row_base=0, eig_s_edge=None, eig_d_edge=None) -> torch.Tensor:
+    """float64 ``[len(channels), E]`` in CSR slot order: the weight every directional aggregator above gives slot j of row i,
+
+        ABSNORM  (kind 0)  ``_abs_normalised``                       (agg_dir_dx, agg_dir_dx_no_abs; agg_dir_av uses its absolute value)
+        BALANCED (kind 1)  ``_balanced_pair``                        (agg_dir_dx_balanced)
+        SOFTMAX  (kind 2)  softmax over the row of alpha * |delta|   (agg_dir_softmax)
+
+    computed in fp64 from the fp32 ``eig`` values (promoted, never rounded again), one in-degree bucket at a time like
+    ``aggregate_graph``.  ``indptr [n + 1]`` / ``src [E]``: destination-major CSR; row i is node ``row_base + i`` of ``eig [N, K]``
+    (a destination-range shard), sources are global ids.  ``channels``: ``(kind, eig column, alpha)`` tuples.  Slot mode: ``eig_s_edge`` /
+    ``eig_d_edge [E, K]`` hold both endpoints of every slot and ``eig`` is not read."""
+    ip = torch.as_tensor(np.asarray(indptr)).long()
+    n, E = ip.numel() - 1, int(ip[-1])
+    if eig_s_edge is not None:
+        es_all, ed_all = torch.as_tensor(eig_s_edge).double(), torch.as_tensor(eig_d_edge).double()
+    else:
+        e64 = torch.as_tensor(eig).double()
+        dst = torch.repeat_interleave(torch.arange(n), ip[1:] - ip[:-1])
+        es_all, ed_all = e64[torch.as_tensor(np.asarray(src)).long()], e64[dst + row_base]
+    w = torch.zeros((len(channels), E), dtype=torch.float64)
+    deg = ip[1:] - ip[:-1]
+    for D in torch.unique(deg).tolist():
+        if D == 0:
+            continue
+        rows = torch.nonzero(deg == D).flatten()
+        slots = (ip[rows].unsqueeze(1) + torch.arange(D).unsqueeze(0)).reshape(-1)
+        es, ed = es_all[slots].reshape(len(rows), D, -1), ed_all[slots].reshape(len(rows), D, -1)
+        for c, (kind, k, alpha) in enumerate(channels):
+            if kind == W_ABSNORM:
+                wc = _abs_normalised(es, ed, k)
+            elif kind == W_BALANCED:
+                wc = _balanced_pair(es, ed, k)
+            elif kind == W_SOFTMAX:
+                wc = torch.softmax(alpha * _delta(es, ed, k).abs().unsqueeze(-1), dim=1)      # agg_dir_softmax's
+            else:
+                raise ValueError(f"unknown channel kind {kind}")
+            w[c, slots] = wc.reshape(-1)
+    return w
 
 
 _PLAIN = {"mean": agg_mean, "sum": agg_sum, "max": agg_max, "min": agg_min,

@@ -63,6 +63,20 @@ def test_argument_validation_without_gpu(lib):
     assert rc == -1
 
 
+def test_edge_weight_route_switches_are_library_options(lib):
+    """ew_big_min / ew_separate / ew_no_flat8 (DGN_EW_BIG_MIN, DGN_EW_SEPARATE, DGN_EW_NO_FLAT8) sit in the option table: read per call of
+    dgn_edge_weights, so a test can flip them (tests/test_edge_weights_gpu.py does) and gets the defaults back."""
+    from dgn_amd import _lib
+    for name, env, default in (("ew_big_min", "DGN_EW_BIG_MIN", 1 << 19), ("ew_separate", "DGN_EW_SEPARATE", 0), ("ew_no_flat8", "DGN_EW_NO_FLAT8", 0)):
+        if env in os.environ:
+            continue                                            # (the caller's environment chose a route: its value is the process's default)
+        assert lib.dgn_get_option(name.encode()) == default, name
+        assert lib.dgn_set_option(name.encode(), 7) == 0 and getattr(_lib.options, name) == 7
+        setattr(_lib.options, name, default)
+        assert lib.dgn_get_option(name.encode()) == default
+    assert lib.dgn_get_option(b"ew_no_such_switch") == -2 ** 63 and lib.dgn_set_option(b"ew_no_such_switch", 1) == -1
+
+
 def test_plan_and_registry():
     import dgn_amd
     from dgn_amd import spec
