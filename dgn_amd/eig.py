@@ -90,9 +90,28 @@ def _bucketed_eigh(src: torch.Tensor, dst: torch.Tensor, sizes: Sequence[int], k
     return out, vals
 
 
-# ---- small graphs: the whole batch in one Jacobi kernel (csrc/dgn_eig_small.hip) ------------------------------------------
+# ---- graphs up to 192 nodes: one Jacobi workgroup per graph (csrc/dgn_eig_small.hip, csrc/dgn_eig_mid.hip) -----------------------
 
 _NORMS = {"none": 0, "sym": 1, "walk": 2}        # include/dgn_hip.h: DGN_EIG_NORM_*
+_SMALL_MAX, _MID_MAX = 64, 192                   # dgn_eig_small_max_nodes(), dgn_eig_mid_max_nodes()
+
+
+def _eig_buffers(who: str, graph, graph_offsets: torch.Tensor, k: int, out, values, status):
+    """The checked ``(out [N, k] fp32, values [G, k] fp64, status [G] int32)`` of a thin launch: made here as zeros / NaN / 0 where not passed."""
+    dev = graph.device
+    if graph_offsets.dtype != torch.int64 or graph_offsets.device != dev or not graph_offsets.is_contiguous() or graph_offsets.dim() != 1:
+        raise ValueError("graph_offsets: a contiguous int64 [G + 1] tensor on the graph's device")
+    G, N = graph_offsets.numel() - 1, graph.num_nodes
+    if out is None:
+        out = torch.zeros(N, k, dtype=torch.float32, device=dev)
+    if values is None:
+        values = torch.full((G, k), float("nan"), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(G, dtype=torch.int32, device=dev)
+    for t, shape, dt in ((out, (N, k), torch.float32), (values, (G, k), torch.float64), (status, (G,), torch.int32)):
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{who}: a buffer is not a contiguous {dt} {shape} tensor on {dev}")
+    return out, values, status
 
 
 def laplacian_eig_small(graph, graph_offsets: torch.Tensor, k: int, norm: str = "none", *, out: Optional[torch.Tensor] = None,
@@ -107,26 +126,48 @@ def laplacian_eig_small(graph, graph_offsets: torch.Tensor, k: int, norm: str = 
     import ctypes as C
     if norm not in _NORMS:
         raise ValueError(norm)
-    dev = graph.device
-    if graph_offsets.dtype != torch.int64 or graph_offsets.device != dev or not graph_offsets.is_contiguous() or graph_offsets.dim() != 1:
-        raise ValueError("graph_offsets: a contiguous int64 [G + 1] tensor on the graph's device")
-    G, N = graph_offsets.numel() - 1, graph.num_nodes
-    if out is None:
-        out = torch.zeros(N, k, dtype=torch.float32, device=dev)
-    if values is None:
-        values = torch.full((G, k), float("nan"), dtype=torch.float64, device=dev)
-    if status is None:
-        status = torch.zeros(G, dtype=torch.int32, device=dev)
-    for t, shape, dt in ((out, (N, k), torch.float32), (values, (G, k), torch.float64), (status, (G,), torch.int32)):
-        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"laplacian_eig_small: a buffer is not a contiguous {dt} {shape} tensor on {dev}")
+    out, values, status = _eig_buffers("laplacian_eig_small", graph, graph_offsets, k, out, values, status)
+    dev, G = graph.device, graph_offsets.numel() - 1
     _lib.check(_lib.load().dgn_eig_small(C.byref(graph.c_graph), graph_offsets.data_ptr(), G, int(k), _NORMS[norm], int(max_sweeps),
                                          out.data_ptr(), values.data_ptr(), status.data_ptr(), _lib.stream_ptr(dev)), "dgn_eig_small")
     return out, values, status
 
 
+def laplacian_eig_mid(graph, graph_offsets: torch.Tensor, k: int, norm: str = "none", *, graph_ids: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None, values: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+                      workspace: Optional[torch.Tensor] = None, max_sweeps: int = 30):
+    """The thin launch of ``dgn_eig_mid`` (csrc/dgn_eig_mid.hip): the ``k`` lowest Laplacian eigenpairs of every graph of 65 to 192 nodes,
+    one workgroup per graph, nothing read back (usable under ``torch.cuda.graph`` when ``workspace`` is preallocated).  Arguments and
+    returns as ``laplacian_eig_small``; a graph of at most 64 nodes is not touched (``status`` 0 when the buffer is made here), one of more
+    than 192 gets ``-1``.  Called after ``laplacian_eig_small`` on the same ``out`` / ``values`` / ``status`` the two cover every graph up to
+    192 nodes: the small call's ``-1`` is overwritten.  ``graph_ids``: device int32 indices of the graphs to solve, one workgroup and one
+    log slot each (default: every graph).  ``workspace``: a uint8 tensor of ``dgn_eig_mid_workspace_bytes(slots, max_sweeps)`` bytes --
+    ``max_sweeps * 146 688`` per slot -- made here when none is passed."""
+    from . import _lib
+    import ctypes as C
+    if norm not in _NORMS:
+        raise ValueError(norm)
+    out, values, status = _eig_buffers("laplacian_eig_mid", graph, graph_offsets, k, out, values, status)
+    dev, G = graph.device, graph_offsets.numel() - 1
+    n_ids = 0
+    if graph_ids is not None:
+        if graph_ids.dtype != torch.int32 or graph_ids.device != dev or not graph_ids.is_contiguous() or graph_ids.dim() != 1:
+            raise ValueError("graph_ids: a contiguous int32 [n_ids] tensor on the graph's device")
+        n_ids = graph_ids.numel()
+    lib = _lib.load()
+    slots = n_ids if graph_ids is not None else G
+    if workspace is None:
+        workspace = torch.empty(max(int(lib.dgn_eig_mid_workspace_bytes(slots, int(max_sweeps))), 1), dtype=torch.uint8, device=dev)
+    if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"laplacian_eig_mid: workspace is not a contiguous uint8 tensor on {dev}")
+    _lib.check(lib.dgn_eig_mid(C.byref(graph.c_graph), graph_offsets.data_ptr(), G, graph_ids.data_ptr() if graph_ids is not None else None,
+                               n_ids, int(k), _NORMS[norm], int(max_sweeps), out.data_ptr(), values.data_ptr(), status.data_ptr(),
+                               workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(dev)), "dgn_eig_mid")
+    return out, values, status
+
+
 def _eigh_fallback(graph, off: torch.Tensor, big, k: int, norm: str, eig: torch.Tensor, values: torch.Tensor) -> None:
-    """Fill the rows and eigenvalues of the graphs ``big`` (more than 64 nodes) from the bucketed ``eigh`` on their sub-batch."""
+    """Fill the rows and eigenvalues of the graphs ``big`` (those no Jacobi kernel solved) from the bucketed ``eigh`` on their sub-batch."""
     dev = graph.device
     G = off.numel() - 1
     sizes = off[1:] - off[:-1]
@@ -142,14 +183,17 @@ def _eigh_fallback(graph, off: torch.Tensor, big, k: int, norm: str, eig: torch.
     values[torch.as_tensor(big, device=dev)] = lam
 
 
-def batch_eig(graph, sizes=None, k: int = 6, norm: str = "none", check: bool = True, *, max_sweeps: int = 30):
+def batch_eig(graph, sizes=None, k: int = 6, norm: str = "none", check: bool = True, *, max_sweeps: int = 30, mid: Optional[bool] = None):
     """``(eig [N, k] fp32, values [G, k] fp64)``: the k lowest Laplacian eigenvectors of every graph of a batch -- what
     ``get_eig`` stores in ``g.ndata['eig']`` (data/molecules.py:100-116) -- and their eigenvalues (``get_eig_val``,
     data/multiplicity_eig.py:14-27).  ``graph``: a ``DGNGraph`` or anything ``as_dgn_graph`` accepts; ``sizes``: the graphs'
     node counts (host list or tensor; default: the graph's ``batch_num_nodes``).  Graphs of at most 64 nodes are solved by
-    ``dgn_eig_small`` in one launch pair.  ``check=True`` reads the statuses back once: an edge from outside a graph's node
-    range or a solve that did not converge raises, graphs of more than 64 nodes go through ``laplacian_eigvecs``.
-    ``check=False`` reads nothing back: the rows of such graphs stay zero, their eigenvalues NaN."""
+    ``dgn_eig_small`` in one launch pair.  ``mid`` (default: as ``check``): the graphs of 65 to 192 nodes, picked from the host
+    ``sizes``, are solved by ``dgn_eig_mid`` in a second launch pair over exactly those, with a log workspace of
+    ``max_sweeps * 146 688`` bytes per such graph that is freed afterwards.  ``check=True`` reads the statuses back once: an edge
+    from outside a graph's node range or a solve that did not converge raises, graphs no kernel solved (more than 192 nodes;
+    more than 64 with ``mid=False``) go through ``laplacian_eigvecs``.  ``check=False`` reads nothing back: the rows of unsolved
+    graphs stay zero, their eigenvalues NaN."""
     from . import _lib
     from .graph import DGNGraph, as_dgn_graph
     if norm not in _NORMS:
@@ -169,7 +213,13 @@ def batch_eig(graph, sizes=None, k: int = 6, norm: str = "none", check: bool = T
     off[1:] = torch.cumsum(sizes_t, 0)
     if int(off[-1]) != graph.num_nodes:
         raise ValueError(f"batch_eig: the sizes add up to {int(off[-1])} nodes, the graph has {graph.num_nodes}")
-    eig, values, status = laplacian_eig_small(graph, off.to(graph.device), k, norm, max_sweeps=max_sweeps)
+    off_dev = off.to(graph.device)
+    eig, values, status = laplacian_eig_small(graph, off_dev, k, norm, max_sweeps=max_sweeps)
+    if check if mid is None else mid:
+        ids = torch.nonzero((sizes_t > _SMALL_MAX) & (sizes_t <= _MID_MAX)).flatten().to(torch.int32)      # host sizes: no read-back
+        if ids.numel():
+            laplacian_eig_mid(graph, off_dev, k, norm, graph_ids=ids.to(graph.device), out=eig, values=values, status=status,
+                              max_sweeps=max_sweeps)
     if not check:
         return eig, values
     st = status.cpu()

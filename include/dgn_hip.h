@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DGN_ABI_VERSION 32
+#define DGN_ABI_VERSION 33
 
 #define DGN_MAX_AGG 16     /* aggregators per launch (the host splits longer lists)            */
 #define DGN_MAX_CH 4       /* edge-weight channels per launch                                   */
@@ -876,6 +876,23 @@ enum { DGN_EIG_NORM_NONE = 0, DGN_EIG_NORM_SYM = 1, DGN_EIG_NORM_WALK = 2 };
 int dgn_eig_small(const DgnGraph* graph, const int64_t* graph_off, int n_graphs, int k, int norm, int max_sweeps, float* vec, double* val,
                   int32_t* status, void* stream);
 int dgn_eig_small_max_nodes(void);
+
+/* ---- ... of the graphs of 65 to 192 nodes (dgn_eig_mid.hip) -----------------------------------------------------------------------------
+ * The same build, solve, stop rule, epilogue and outputs as dgn_eig_small for the graphs it answers with -1, up to 192 nodes (CLUSTER's
+ * largest graph has 190, PATTERN's 188, CIFAR10's 150).  One workgroup per graph, the matrix packed symmetric in LDS in fp64, no eigenvector
+ * matrix: every rotation's tangent goes to the graph's log slot in `ws` and the k kept vectors are formed by replaying the log backwards.
+ *     graph_ids  DEVICE [n_ids] graph indices or NULL.  Workgroup (= log slot) s solves graph graph_ids[s]; NULL: every graph, slot = graph
+ *                index, n_ids ignored.  An entry outside [0, n_graphs) is skipped; no graph may be listed twice.
+ *     ws         dgn_eig_mid_workspace_bytes(slots, max_sweeps) bytes, slots = n_ids (n_graphs for NULL graph_ids):
+ *                slots * max_sweeps * 191 * 96 * 8.  Too small for the sweep cap: DGN_ERR_WORKSPACE, nothing launched.
+ *     status     sweeps done (>= 1), -1: more than 192 nodes, -2 as dgn_eig_small; a graph of at most 64 nodes is NOT touched (status, vec and
+ *                val keep what they held): launched after dgn_eig_small on the same buffers the two cover every graph up to 192 nodes.
+ * Two launches over the slots ((64, 128] nodes: 512 threads, (128, 192]: 1024 threads and 156 304 bytes of LDS; a device that grants a
+ * workgroup less: DGN_ERR_INVALID on the first call), nothing read back, capturable.  A graph's output bits depend on the graph alone. */
+int dgn_eig_mid_max_nodes(void);
+size_t dgn_eig_mid_workspace_bytes(int n_slots, int max_sweeps);
+int dgn_eig_mid(const DgnGraph* graph, const int64_t* graph_off, int n_graphs, const int32_t* graph_ids, int n_ids, int k, int norm,
+                int max_sweeps, float* vec, double* val, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
