@@ -13,10 +13,12 @@ from .dgn_layer import (AGGREGATORS, SCALERS, DGNLayer, DGNLayerComplex, DGNLaye
 from .readout import VirtualNode, max_nodes, mean_nodes, readout, sum_nodes
 from .eig import laplacian_eigvecs, laplacian_eig_small, laplacian_eig_mid, batch_eig, positional_encoding, eig_multiplicity
 from .ops import balanced_cross_entropy, masked_bce_with_logits, mlp_head, multi_embedding
+from .superpixels import coord_encoding, knn_edge_counts, knn_graph, sort_eig, superpixel_eig
 from .nets import AtomEncoder, BondEncoder, DGNHIVNet, DGNNet, DGNNodeNet, DGNPCBANet, accuracy_sbm, ap_ogb, rocauc_ogb
 
 __all__ = ["DGNGraph", "as_dgn_graph", "compute_edge_weights", "make_plan", "directional_aggregate", "FCLayer", "MLP",
            "get_activation", "AGGREGATORS", "SCALERS", "DGNLayer", "DGNLayerSimple", "DGNLayerComplex", "DGNLayerTower",
            "DGNTower", "EdgeTypeFeatures", "AGGREGATOR_NAMES", "SCALER_NAMES", "VirtualNode", "sum_nodes", "mean_nodes", "max_nodes", "readout",
            "laplacian_eigvecs", "laplacian_eig_small", "laplacian_eig_mid", "batch_eig", "positional_encoding", "eig_multiplicity", "balanced_cross_entropy", "DGNNet", "DGNNodeNet", "accuracy_sbm",
-           "multi_embedding", "masked_bce_with_logits", "mlp_head", "AtomEncoder", "BondEncoder", "DGNHIVNet", "DGNPCBANet", "rocauc_ogb", "ap_ogb"]
+           "multi_embedding", "masked_bce_with_logits", "mlp_head", "AtomEncoder", "BondEncoder", "DGNHIVNet", "DGNPCBANet", "rocauc_ogb", "ap_ogb",
+           "knn_edge_counts", "knn_graph", "coord_encoding", "sort_eig", "superpixel_eig"]

@@ -14,7 +14,7 @@ import threading
 DGN_MAX_AGG = 16
 DGN_MAX_CH = 4
 DGN_MAX_SCALERS = 4
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 LIB_PATH = os.environ.get("DGN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdgn_hip.so")
 
@@ -40,7 +40,8 @@ EXPORTS = ("dgn_abi_version", "dgn_sizeof", "dgn_last_error", "dgn_set_option", 
            "dgn_multi_embedding_supported", "dgn_multi_embedding_backward_workspace_bytes", "dgn_multi_embedding_forward", "dgn_multi_embedding_backward",
            "dgn_masked_bce_workspace_bytes", "dgn_masked_bce_forward", "dgn_masked_bce_backward",
            "dgn_mlp_head_supported", "dgn_mlp_head_forward", "dgn_mlp_head_backward_workspace_bytes", "dgn_mlp_head_backward",
-           "dgn_eig_small", "dgn_eig_small_max_nodes", "dgn_eig_mid", "dgn_eig_mid_max_nodes", "dgn_eig_mid_workspace_bytes")
+           "dgn_eig_small", "dgn_eig_small_max_nodes", "dgn_eig_mid", "dgn_eig_mid_max_nodes", "dgn_eig_mid_workspace_bytes",
+           "dgn_knn_graph_max_nodes", "dgn_knn_graph", "dgn_superpixel_sort_eig")
 
 DGN_DC_CLASSES, DGN_DC_UNIT = 32, 64
 
@@ -410,6 +411,12 @@ def load() -> C.CDLL:
         lib.dgn_eig_mid_max_nodes.argtypes = []
         lib.dgn_eig_mid_workspace_bytes.restype = C.c_size_t
         lib.dgn_eig_mid_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        lib.dgn_knn_graph_max_nodes.restype = C.c_int
+        lib.dgn_knn_graph_max_nodes.argtypes = []
+        lib.dgn_knn_graph.restype = C.c_int
+        lib.dgn_knn_graph.argtypes = [vp, vp, C.c_int, C.c_int64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp, vp, vp, vp]
+        lib.dgn_superpixel_sort_eig.restype = C.c_int
+        lib.dgn_superpixel_sort_eig.argtypes = [vp, C.c_int64, C.c_int, vp, vp, C.c_int64, vp, C.c_int, vp]
         if lib.dgn_abi_version() != ABI_VERSION:
             raise DgnError(f"libdgn_hip.so ABI {lib.dgn_abi_version()} != binding {ABI_VERSION}: rebuild")
         _lib = lib

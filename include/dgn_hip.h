@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DGN_ABI_VERSION 33
+#define DGN_ABI_VERSION 34
 
 #define DGN_MAX_AGG 16     /* aggregators per launch (the host splits longer lists)            */
 #define DGN_MAX_CH 4       /* edge-weight channels per launch                                   */
@@ -893,6 +893,39 @@ int dgn_eig_mid_max_nodes(void);
 size_t dgn_eig_mid_workspace_bytes(int n_slots, int max_sweeps);
 int dgn_eig_mid(const DgnGraph* graph, const int64_t* graph_off, int n_graphs, const int32_t* graph_ids, int n_ids, int k, int norm,
                 int max_sweeps, float* vec, double* val, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- superpixel k-NN graphs and the sort_eig column choice (dgn_superpixels.hip) --------------------------------------------------------
+ * dgn_knn_graph replaces the per-graph host work of the reference's superpixel loader: sigma, compute_adjacency_matrix_images and
+ * compute_edges_list (data/superpixels.py:17-69: cdist, two np.partition calls and an exp per graph) with the self-edge removal of
+ * SuperPixDGL._prepare (:139-145).  coord: [n_nodes, 2] fp64 (already divided by the image size); feat: [n_nodes, n_feat] fp64, 1 <= n_feat <= 8,
+ * or NULL with n_feat = 0 (coordinates only: use_feat=False); graph_off / edge_off: DEVICE [n_graphs + 1] node / edge offsets.  Per graph of
+ * n nodes, in fp64 and in the reference's order of operations: d_c, d_f the Euclidean distances of coordinates / features,
+ * sigma(i) = (sum of the k + 1 smallest entries of row i, the zero diagonal included) / k + 1e-8 for n >= k + 1, else 1 + 1e-8,
+ * E(i, j) = exp(-(d_c / sigma_c(i))^2 - (d_f / sigma_f(i))^2), A = (E + E^T) / 2 with a zero diagonal.  Edges:
+ *     n >= k + 2       the n - 1 other nodes of row i ranked by A descending, equal values by lower column; skip_nearest = 1 emits ranks 1 .. k
+ *                      -- the reference's np.argpartition(A, n - 10)[:, n - 9:-1] at k = 8: it LEAVES OUT the most similar node --,
+ *                      skip_nearest = 0 ranks 0 .. k - 1; k edges per node in rank order
+ *     2 <= n <= k + 1  every j != i in ascending j: n - 1 edges per node
+ *     n == 1           one self-loop of value 0
+ *     src, dst   [n_edges] int64: edge edge_off[g] + i * per_node + slot has src = n0 + i (row i is the sender: g.add_edges(src, dsts)), dst = n0 + j
+ *     value      [n_edges] fp32: (float) A(i, j), the reference's edge feature
+ *     status     [n_graphs]: 0 ok, -1: more than dgn_knn_graph_max_nodes() = 256 nodes, -2: a node or edge range outside the arrays or an
+ *                edge_off span that is not the count of the rule above.  A graph with a negative status has nothing else written.
+ * 1 <= k <= 32.  One launch, one workgroup of 256 threads per graph, nothing read back, capturable; a graph's output bits depend on the graph
+ * alone.  n_graphs == 0: no-op.
+ *
+ * dgn_superpixel_sort_eig replaces sort_eig / get_scores (data/superpixels.py:371-420) on eig [n_nodes, n_cols] fp32 (row stride ld_eig,
+ * n_cols >= 3) with the nodes' coordinates x, y [n_nodes] fp32: for column c in {1, 2}, hor_c = |sum over eig[i, c] > 0 of (x_i > 0.5 ? 1 : -1)|,
+ * ver_c likewise with y, m the largest of the four.  hor_1 == m or ver_2 == m: the graph's rows stay.  Otherwise column 1 of its rows is
+ * overwritten with column 2, in place: what the reference's two exchanging arms leave (eigs[:, 1] = eig2; eigs[:, 2] = eig1 with eig1 a VIEW of
+ * column 1 -- column 2 ends up in both columns; fixture G15 holds the reference's output).  One launch, a wave per graph, no status: a graph
+ * whose node range lies outside [0, n_nodes] is skipped.  Nothing read back, capturable.  n_graphs == 0: no-op. */
+int dgn_knn_graph_max_nodes(void);
+int dgn_knn_graph(const double* coord, const double* feat, int n_feat, int64_t n_nodes, const int64_t* graph_off,
+                  const int64_t* edge_off, int n_graphs, int k, int skip_nearest, int64_t n_edges,
+                  int64_t* src, int64_t* dst, float* value, int32_t* status, void* stream);
+int dgn_superpixel_sort_eig(float* eig, int64_t ld_eig, int n_cols, const float* x, const float* y,
+                            int64_t n_nodes, const int64_t* graph_off, int n_graphs, void* stream);
 
 #ifdef __cplusplus
 }
