@@ -25,6 +25,8 @@ from typing import Optional, Sequence
 
 import torch
 
+from . import _lib
+
 _PAD = 1.0e4      # diagonal of the padding rows: far above any Laplacian eigenvalue (<= 2 * max degree)
 
 
@@ -92,7 +94,7 @@ def _bucketed_eigh(src: torch.Tensor, dst: torch.Tensor, sizes: Sequence[int], k
 
 # ---- graphs up to 192 nodes: one Jacobi workgroup per graph (csrc/dgn_eig_small.hip, csrc/dgn_eig_mid.hip) -----------------------
 
-_NORMS = {"none": 0, "sym": 1, "walk": 2}        # include/dgn_hip.h: DGN_EIG_NORM_*
+_NORMS = {"none": _lib.DGN_EIG_NORM_NONE, "sym": _lib.DGN_EIG_NORM_SYM, "walk": _lib.DGN_EIG_NORM_WALK}
 _SMALL_MAX, _MID_MAX = 64, 192                   # dgn_eig_small_max_nodes(), dgn_eig_mid_max_nodes()
 
 
@@ -122,7 +124,6 @@ def laplacian_eig_small(graph, graph_offsets: torch.Tensor, k: int, norm: str = 
     int32)``: ``status`` is the number of Jacobi sweeps, ``-1`` for a graph of more than 64 nodes, ``-2`` for one with an
     edge from outside its node range -- the rows of such graphs keep what ``out`` / ``values`` held (zeros / NaN when the
     buffers are made here)."""
-    from . import _lib
     import ctypes as C
     if norm not in _NORMS:
         raise ValueError(norm)
@@ -143,7 +144,6 @@ def laplacian_eig_mid(graph, graph_offsets: torch.Tensor, k: int, norm: str = "n
     192 nodes: the small call's ``-1`` is overwritten.  ``graph_ids``: device int32 indices of the graphs to solve, one workgroup and one
     log slot each (default: every graph).  ``workspace``: a uint8 tensor of ``dgn_eig_mid_workspace_bytes(slots, max_sweeps)`` bytes --
     ``max_sweeps * 146 688`` per slot -- made here when none is passed."""
-    from . import _lib
     import ctypes as C
     if norm not in _NORMS:
         raise ValueError(norm)
@@ -194,7 +194,6 @@ def batch_eig(graph, sizes=None, k: int = 6, norm: str = "none", check: bool = T
     from outside a graph's node range or a solve that did not converge raises, graphs no kernel solved (more than 192 nodes;
     more than 64 with ``mid=False``) go through ``laplacian_eigvecs``.  ``check=False`` reads nothing back: the rows of unsolved
     graphs stay zero, their eigenvalues NaN."""
-    from . import _lib
     from .graph import DGNGraph, as_dgn_graph
     if norm not in _NORMS:
         raise ValueError(norm)

@@ -30,7 +30,7 @@ HUB_CHUNK = 1024
 # True: a graph given as CUDA edge lists is prepared by dgn_graph_build* (a handful of kernels behind one C call each);
 # False: the same arrays from ~40 torch ops (what CPU tensors -- the gloo tests -- always use).  Same results.
 NATIVE_BUILD = True
-DC_CLASSES, DC_UNIT = 32, 64      # include/dgn_hip.h: DGN_DC_CLASSES, DGN_DC_UNIT
+DC_CLASSES, DC_UNIT = _lib.DGN_DC_CLASSES, _lib.DGN_DC_UNIT
 GRAPH_BLOCK_MAX_ROWS = 512       # largest graph (nodes) of a batch for which the graph backward is attached (the C side checks the LDS per list / width)
 BLOCK_MAX_GAP = 52         # largest graph of a batch (nodes) for which the block backward is tried (a wave's block is at most 56 rows: csrc/dgn_agg_block.hpp; the C side checks the LDS budget per F)
 DEFERRED_STATS = True      # DGNGraph.rebuild: the batch's (max in-degree, hub rows) are checked at the next load instead of with a host sync

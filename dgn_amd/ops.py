@@ -103,7 +103,7 @@ def _ld(t: Optional[torch.Tensor]) -> int:
     return 0 if t is None else (t.stride(0) if t.shape[0] > 1 else t.shape[1])
 
 
-MAX_EDGE_TABLE = 8192      # include/dgn_hip.h: DGN_MAX_EDGE_TABLE (floats of an edge-type table)
+MAX_EDGE_TABLE = _lib.DGN_MAX_EDGE_TABLE      # floats of an edge-type table
 
 
 def _msg_struct(F, x_src, x_dst, m_edge, x_in, edge_type=None, f_valid=0):
@@ -1903,7 +1903,7 @@ def balanced_cross_entropy(scores: torch.Tensor, labels: torch.Tensor, n_classes
 
 # ---- OGB molecule nets: multi-column embedding sum, masked BCE with logits (dgn_mol_io.hip) ------------------------------------------
 
-MULTI_EMBEDDING_MAX_COLS = 16      # include/dgn_hip.h: DGN_MULTI_EMBEDDING_MAX_COLS
+MULTI_EMBEDDING_MAX_COLS = _lib.DGN_MULTI_EMBEDDING_MAX_COLS
 
 
 def _i32_array(values):

@@ -13,14 +13,15 @@ from dataclasses import dataclass, field
 from typing import List, Sequence, Tuple
 
 from . import _lib
+# op codes (the enums of include/dgn_hip.h)
+from ._lib import (DGN_AGG_MEAN as AGG_MEAN, DGN_AGG_SUM as AGG_SUM, DGN_AGG_MAX as AGG_MAX, DGN_AGG_MIN as AGG_MIN, DGN_AGG_STD as AGG_STD,
+                   DGN_AGG_VAR as AGG_VAR, DGN_AGG_DIR_AV as AGG_DIR_AV, DGN_AGG_DIR_WSUM as AGG_DIR_WSUM, DGN_AGG_DIR_DX as AGG_DIR_DX,
+                   DGN_AGG_DIR_DX_NO_ABS as AGG_DIR_DX_NO_ABS, DGN_AGG_X_IN as AGG_X_IN)
+from ._lib import DGN_W_ABSNORM as W_ABSNORM, DGN_W_BALANCED as W_BALANCED, DGN_W_SOFTMAX as W_SOFTMAX
+from ._lib import DGN_SCALE_IDENTITY as SCALE_IDENTITY, DGN_SCALE_AMPLIFICATION as SCALE_AMPLIFICATION, DGN_SCALE_ATTENUATION as SCALE_ATTENUATION
 
 EPS = 1e-8  # aggregators.py:5
-
-# op codes (include/dgn_hip.h)
-AGG_MEAN, AGG_SUM, AGG_MAX, AGG_MIN, AGG_STD, AGG_VAR, AGG_DIR_AV, AGG_DIR_WSUM, AGG_DIR_DX, AGG_DIR_DX_NO_ABS, AGG_X_IN = range(11)
 X_IN_NAME = "__x_in__"     # pseudo-aggregator: copies h_in into the output row (posttrans([h || agg]) becomes one GEMM)
-W_ABSNORM, W_BALANCED, W_SOFTMAX = range(3)
-SCALE_IDENTITY, SCALE_AMPLIFICATION, SCALE_ATTENUATION = range(3)
 
 _PLAIN = {"mean": AGG_MEAN, "sum": AGG_SUM, "max": AGG_MAX, "min": AGG_MIN, "std": AGG_STD, "var": AGG_VAR}
 _DIR_RE = re.compile(r"^dir([1-3])-(av|smooth|dx|dx-no-abs|dx-balanced|0\.1|neg-0\.1)$")

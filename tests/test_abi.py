@@ -28,24 +28,116 @@ def test_header_symbols_are_exported(lib):
     for sym in declared:
         assert getattr(lib, sym) is not None
     assert lib.dgn_abi_version() == _lib.ABI_VERSION
+    # no function is left on ctypes' defaults: argtypes are set, as many as the prototype has parameters by this test's own regex
+    protos = dict(re.findall(r"\b(dgn_[a-z_]+)\s*\(([^()]*)\)\s*;", re.sub(r"/\*.*?\*/", " ", header, flags=re.S)))
+    assert list(protos) == list(_lib.EXPORTS)                       # header order
+    for sym, params in protos.items():
+        argtypes = getattr(lib, sym).argtypes
+        assert argtypes is not None and len(argtypes) == (0 if params.strip() == "void" else params.count(",") + 1), sym
 
 
 def test_struct_layouts_match_header(lib):
     from dgn_amd import _lib
-    # every ctypes mirror against the sizeof the LIBRARY was compiled with (dgn_sizeof), then a few sizes spelled out for LP64
-    for name in ("DgnGraph", "DgnChannel", "DgnAggSpec", "DgnMsg", "DgnMsgGrad", "DgnBnGrad", "DgnTowersLayer", "DgnTowersGrads", "DgnDegreeClasses",
-                 "DgnDcLayout", "DgnDenseLayer", "DgnDenseGrads", "DgnBlockTable", "DgnBlockLayer", "DgnBlockGrads"):
-        assert C.sizeof(getattr(_lib, name)) == lib.dgn_sizeof(name.encode()) > 0, name
+    # every struct the binding derived against the sizeof the LIBRARY was compiled with (dgn_sizeof; 0 for a struct the header has and
+    # dgn_sizeof forgot), then a few sizes spelled out for LP64
+    header = open(os.path.join(ROOT, "include", "dgn_hip.h")).read()
+    structs = {name: t for name, t in vars(_lib).items() if isinstance(t, type) and issubclass(t, C.Structure)}
+    assert set(structs) == set(re.findall(r"typedef\s+struct\s+(\w+)", header)) and len(structs) >= 15
+    for name, t in structs.items():
+        assert C.sizeof(t) == lib.dgn_sizeof(name.encode()) > 0, name
     assert lib.dgn_sizeof(b"NoSuchStruct") == 0
     assert C.sizeof(_lib.DgnChannel) == 16
     assert C.sizeof(_lib.DgnGraph) == 8 * 9 + 4 * 2 + 8 * 2 + 8 + 8 + 8 + 8 + 8 + 8 * 5       # (+ max_in_degree padded, n_src, row_base, blk_cut, blk_gap padded; gblk_desc, n_gblk, gblk_rows padded, csc_order, dst_csr)
     assert C.sizeof(_lib.DgnAggSpec) == 4 * (1 + 16 + 16 + 1 + 1 + 4 + 1 + 1 + 1 + 1 + 1) + 8
     assert C.sizeof(_lib.DgnMsg) == 8 * 9 + 8 + 8                               # (+ edge_type, n_edge_types padded)
     assert C.sizeof(_lib.DgnMsgGrad) == 8 * 8 + 8                                # (+ accumulate, padded)
-    header = open(os.path.join(ROOT, "include", "dgn_hip.h")).read()
     assert f"#define DGN_MAX_AGG {_lib.DGN_MAX_AGG}" in header
     assert f"#define DGN_MAX_CH {_lib.DGN_MAX_CH}" in header
     assert f"#define DGN_MAX_SCALERS {_lib.DGN_MAX_SCALERS}" in header
+
+
+_MINI = """
+/* a comment with a prototype inside: int dgn_not_real(int x); */
+#ifndef MINI_H
+#define MINI_H
+#include <stddef.h>
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define DGN_N 3   /* array length */
+enum { DGN_A = 0, DGN_B = -2 };
+enum {
+    DGN_C = 7    /* the last enumerator has no comma */
+};
+typedef struct DgnInner { int32_t a, b, c[DGN_N]; float x, y; } DgnInner;
+typedef struct DgnOuter {
+    const DgnInner* inner;      /* a struct pointer */
+    const float* const* tables; float* out; int64_t ld;   /* several fields on one line */
+    uint64_t offset; size_t bytes; unsigned char* mask; int64_t pad[2];
+} DgnOuter;
+const char* dgn_text(void);
+size_t dgn_bytes(const DgnOuter* o, uint64_t offset,
+                 const float* const* tables, const char* name, double* val, int k, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif /* MINI_H */
+"""
+
+
+def test_header_parser_reads_every_construct_of_the_header():
+    from dgn_amd import _cabi
+    h = _cabi.parse(_MINI)
+    assert h.constants == {"DGN_N": 3, "DGN_A": 0, "DGN_B": -2, "DGN_C": 7}
+    inner, outer = h.structs["DgnInner"], h.structs["DgnOuter"]
+    assert list(h.structs) == ["DgnInner", "DgnOuter"] and issubclass(outer, C.Structure)
+    assert inner._fields_ == [("a", C.c_int32), ("b", C.c_int32), ("c", C.c_int32 * 3), ("x", C.c_float), ("y", C.c_float)]      # multi-declarator, #define-sized array
+    assert outer._fields_ == [("inner", C.POINTER(inner)), ("tables", C.POINTER(C.c_void_p)), ("out", C.c_void_p), ("ld", C.c_int64),
+                              ("offset", C.c_uint64), ("bytes", C.c_size_t), ("mask", C.c_void_p), ("pad", C.c_int64 * 2)]
+    assert C.sizeof(inner) == 28 and C.sizeof(outer) == 8 * 9
+    assert list(h.prototypes) == ["dgn_text", "dgn_bytes"]                                      # the one inside the comment is no declaration
+    assert h.prototypes["dgn_text"] == (C.c_char_p, [])
+    assert h.prototypes["dgn_bytes"] == (C.c_size_t, [C.POINTER(outer), C.c_uint64, C.POINTER(C.c_void_p), C.c_char_p, C.c_void_p, C.c_int, C.c_void_p])
+
+
+@pytest.mark.parametrize("text", [
+    "int dgn_f(int128_t x);",                                            # unknown type
+    "typedef struct DgnS { bool flag; } DgnS;",                          # ... in a field
+    "long dgn_f(void);",                                                 # ... as the result
+    "int dgn_f(const DgnNowhere* p);",                                   # pointer to an undeclared struct
+    "typedef struct DgnS { const DgnNowhere* p; } DgnS;",
+    "int dgn_f(DgnS s);\ntypedef struct DgnS { int a; } DgnS;",          # ... declared only later; and by value
+    "int dgn_global;",                                                   # stray declarations
+    "struct DgnS;",
+    "typedef int32_t dgn_index;",
+    "static inline int dgn_f(int x) { return x; }",
+    "#define DGN_F(x) (x)",
+    "#define DGN_HALF 0.5",
+    "#include <stdio.h>",
+    "// a C++ comment",
+    "}",
+    "enum { DGN_A, DGN_B };",                                            # enumerators without values
+    "typedef struct DgnS { int a; } DgnT;",                              # two names
+    "typedef struct DgnS { int a[DGN_UNKNOWN]; } DgnS;",                 # array length that is no #define
+    "typedef struct DgnS { float *a, *b; } DgnS;",                       # pointer declarators sharing a type
+    "typedef struct DgnS { int a : 3; } DgnS;",                          # bit field
+    "int dgn_f(int32_t);",                                               # parameter without a name
+    "int dgn_f(int32_t dims[4]);",                                       # array parameter
+    "int dgn_f(float*** p);",
+    "int dgn_f(int x)",                                                  # no semicolon
+])
+def test_header_parser_raises_on_what_it_does_not_understand(text):
+    from dgn_amd import _cabi
+    with pytest.raises(ValueError, match="dgn_hip.h"):
+        _cabi.parse("#define DGN_N 3\n" + text + "\nint dgn_after(void);\n")
+
+
+def test_missing_header_is_an_error():
+    from dgn_amd import _lib
+    missing = os.path.join(ROOT, "include", "no_such_header.h")
+    with pytest.raises(_lib.DgnError, match="no_such_header.h"):
+        _lib.read_abi(missing)
 
 
 def test_argument_validation_without_gpu(lib):
