@@ -419,7 +419,7 @@ extern "C" int dgn_dense_layer_backward(const DgnDenseLayer* L, const DgnDenseGr
     } else {
         // (one scaler: the bias gradient sum_m g_z[m, :] rides in the weight-gradient pass as its ones column -- no partial sums in the
         //  combine backward, no bias_finalize launch: round 6, the 19-launch CIFAR10 step)
-        const bool bias_from_wgrad = d.S == 1;
+        const bool bias_from_wgrad = d.S == 1 && !L->scale;      // (with a scale table sum_m g_z[m, :] carries the table's factors: not d bias)
         DGN_TRY(scale_combine_backward_impl(d.N, 1, d.S, d.fo, nullptr, 0, L->scale, L->snorm, g_z, bias_from_wgrad ? nullptr : G->g_b_post, ws + s.comb_ws,
                                            dgn_scale_combine_backward_workspace_bytes(d.N, 1, d.fo), &bn, stream, 1));
         // posttrans: input gradient (on the transposed folded weight), weight gradient, un-folded into the reference's layout

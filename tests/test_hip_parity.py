@@ -668,12 +668,13 @@ def test_bn_tail_on_widths_that_are_no_multiple_of_four(N, W, relu, use_res):
     _close(mine.running_var, ref.running_var.float(), 1e-5, 1e-6)
 
 
-@pytest.mark.parametrize("N,W", [(1003, 75), (997, 65), (5, 75), (3, 70), (4099, 70), (2, 3), (1030, 130)])
+@pytest.mark.parametrize("N,W", [(1003, 75), (997, 65), (5, 75), (3, 70), (4099, 70), (2, 3), (1030, 130), (1003, 258), (7, 1)])
 @pytest.mark.parametrize("relu,with_rows", [(True, True), (False, False)])
 def test_one_tower_combine_bn_tail_on_widths_that_are_no_multiple_of_four(N, W, relu, with_rows):
     """Round 6 (csrc/dgn_combine.hip combine_bwd_flat4): the backward of bias + graph norm + BatchNorm (+ ReLU) of a one-tower, scaler-free
     posttrans output -- the simple / complex layers' tail -- on dense rows of a width that is no multiple of four runs on flat 16-byte
-    chunks.  Against torch in fp64: output, d z, d bias, the affine gradients; ragged row counts, fewer rows than a period."""
+    chunks.  Against torch in fp64: output, d z, d bias, the affine gradients; ragged row counts, fewer rows than a period.  Widths 258 (wider
+    than a workgroup: the flat kernel's epilogue has a thread per column) and 1 (a chunk spans four rows) stay on combine_bwd."""
     dev = _dev()
     from dgn_amd import ops
     gen = torch.Generator().manual_seed(N * 100 + W)
@@ -1043,6 +1044,73 @@ def test_dense_layer_forward_with_batchnorm_statistics_from_the_posttrans_pass(m
     assert torch.equal(ya, yc) and torch.equal(ga, gc)
     for k in ba:
         assert torch.equal(ba[k], bc[k]), k
+
+
+@pytest.mark.parametrize("type_net", ["simple", "complex"])
+@pytest.mark.parametrize("F_", [70, 75])
+def test_dense_layer_with_a_scale_table_of_one_scaler(monkeypatch, type_net, F_):
+    """``ops.dense_layer`` with a random [N, 1] scale table (DgnDenseLayer accepts one scaler WITH a table: y0 = snorm (scale z + b)).  The
+    bias gradient is then sum_n snorm scale-free g, not the column sums of g_z the weight-gradient pass delivers when there is no table
+    (csrc/dgn_layers.hip: bias_from_wgrad).  d b_post, d w_post, d gamma, d beta against an fp64 torch restatement of the layer from the
+    aggregate block onward (the aggregate from ops.directional_aggregate, detached), allowed the error of the same restatement in fp32
+    (parity_util.check_reduced); the output against it at the tolerance of the tests around this one."""
+    dev = _dev()
+    import inspect
+    import dgn_amd
+    from dgn_amd import synth
+    from parity_util import check_reduced
+    monkeypatch.setattr(dgn_amd.ops, "LINEAR_MIN_ROWS", 0)
+    monkeypatch.setattr(dgn_amd.ops, "WHOLE_LAYER_MIN_ROWS", 0)
+    monkeypatch.setattr(dgn_amd.ops, "BLOCK_LAYER_MAX_NODES", 0)
+    b = synth.molecule_batch(40, seed=29, laplacian_eig=False)
+    N = int(b["num_nodes"])
+    graph = dgn_amd.DGNGraph(b["src"].to(dev), b["dst"].to(dev), N, eig=b["eig"].to(dev))
+    torch.manual_seed(14)
+    aggs = "mean max min dir1-av dir1-dx"
+    layer = dgn_amd.DGNLayer(F_, F_, 0.0, True, True, aggs, "identity", {"log": torch.tensor(1.1)}, type_net, True, towers=1, edge_features=False,
+                             edge_dim=0).model.to(dev).train()
+    gen = torch.Generator().manual_seed(6 + F_)
+    h0 = torch.randn(N, F_, generator=gen) * 1.5 + 0.4
+    ct = torch.randn(N, F_, generator=gen)
+    table = torch.rand(N, 1, generator=gen) + 0.5
+    with torch.no_grad():
+        layer.batchnorm_h.weight.copy_(torch.rand(F_, generator=gen) + 0.5)
+        layer.batchnorm_h.bias.copy_(torch.randn(F_, generator=gen) * 0.3)
+    snorm = b["snorm_n"]
+    orig, calls = dgn_amd.ops.dense_layer, []
+
+    def with_table(*a, **k):
+        call = inspect.signature(orig).bind(*a, **k)
+        assert call.arguments["scale"] is None, "one identity scaler: the layer passes no table of its own"
+        call.arguments["scale"] = table.to(dev)
+        calls.append(1)
+        return orig(*call.args, **call.kwargs)
+    monkeypatch.setattr(dgn_amd.ops, "dense_layer", with_table)
+    h = h0.to(dev).requires_grad_(True)
+    y = layer(graph, h, None, snorm.to(dev))
+    y.backward(ct.to(dev))
+    assert len(calls) == 1, "the whole-layer entry point was not taken"
+    lin, bn = layer.posttrans.fully_connected[0].linear, layer.batchnorm_h
+    with torch.no_grad():
+        if type_net == "simple":
+            agg = layer.aggregate(graph, h0.to(dev), layer._kplan, graph.ndata["eig"]).cpu()                 # [N, A F]
+        else:
+            agg = layer.aggregate(graph, h0.to(dev), None, layer._kplan_x, graph.ndata["eig"]).cpu()         # [N, A F | F]
+            agg = torch.cat([agg[:, -F_:], agg[:, :-F_]], dim=1)                                                # the reference's [h || agg]
+    assert agg.shape[1] == lin.weight.shape[1]
+
+    def restate(dtype):
+        w, bp, ga, be = (t.detach().cpu().to(dtype).requires_grad_(True) for t in (lin.weight, lin.bias, bn.weight, bn.bias))
+        y0 = ((agg.to(dtype) @ w.t()) * table.to(dtype) + bp) * snorm.to(dtype).reshape(-1, 1)
+        out = torch.relu(torch.nn.functional.batch_norm(y0, None, None, ga, be, True, 0.1, bn.eps)) + h0.to(dtype)
+        out.backward(ct.to(dtype))
+        return out.detach(), dict(b_post=bp.grad, w_post=w.grad, gamma=ga.grad, beta=be.grad)
+    y64, g64 = restate(torch.float64)
+    _, g32 = restate(torch.float32)
+    _close(y, y64.float(), 3e-5, 3e-5)
+    ours = dict(b_post=lin.bias.grad, w_post=lin.weight.grad, gamma=bn.weight.grad, beta=bn.bias.grad)
+    for k in ("b_post", "w_post", "gamma", "beta"):
+        check_reduced(ours[k], g32[k], g64[k], f"dense layer {type_net} {F_} with a [N, 1] scale table: d {k}")
 
 
 @pytest.mark.parametrize("aggs,T", [("mean max min dir1-av dir1-dx", 5), ("mean max min dir1-dx dir1-av", 1), ("mean max min dir1-av dir1-dx", 1)])
