@@ -71,6 +71,17 @@ hipError_t allow_lds(LdsOptIn& done, int bytes, const void* const* kernels, int 
     return hipSuccess;
 }
 
+int n_cus() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
+        cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    return cus;
+}
+
 int hip_fail(hipError_t e, const char* what) {
     set_error("HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what);
     return DGN_ERR_HIP;

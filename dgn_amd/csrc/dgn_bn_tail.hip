@@ -227,7 +227,6 @@ __device__ __forceinline__ void column_partials_flat4(int64_t n_rows, int F, dou
 }
 // (dense rows, a 16-byte aligned base, a width the thread-per-pair kernels do not take or take at 8 bytes only, a period within one workgroup)
 bool flat4_ok(int F, int64_t ld, const void* a, const void* b = nullptr) {
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     return ld == F && (F & 3) != 0 && F / flat_gcd4(F) <= 256 && al16(a) && al16(b);
 }
 
@@ -511,7 +510,7 @@ unsigned flat_grid(int64_t total) { return (unsigned)std::min<int64_t>((total + 
 void launch_bn_apply(hipStream_t stream, int64_t n_rows, int F, const float* x, int64_t ld, const float* gamma, const float* beta, const float* mean,
                      const float* invstd, const float* running_mean, const float* running_var, float eps, int relu, const float* residual, float* y) {
     const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual);
-    if (flat4_ok(F, ld, x, y) && (reinterpret_cast<uintptr_t>(residual) & 15) == 0) {
+    if (flat4_ok(F, ld, x, y) && al16(residual)) {
         hipLaunchKernelGGL(bn_apply_flat4, dim3(std::max(1u, flat_grid((n_rows * F) >> 2))), dim3(256), 0, stream, n_rows, F, x, gamma, beta, mean, invstd, running_mean,
                            running_var, eps, relu, residual, y);
         return;

@@ -411,7 +411,6 @@ int dgn::scale_combine_backward_impl(int64_t n_nodes, int32_t T, int32_t S, int3
     {   // one tower, no scaler table, dense rows of a width that is no multiple of four, 16-byte aligned: flat 16-byte chunks
         // (2 <= wy <= kThreads: at wy == 1 a chunk spans four rows and the kernel keeps the row_scale of two; its epilogue -- bias partial, the rows
         //  behind the last whole period -- has one thread per column)
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
         if (bn && T == 1 && S == 1 && !scale && (wy & 3) != 0 && wy >= 2 && wy <= kThreads && bn->ld == wy && al16(bn->y) && al16(bn->g_out) &&
             al16(g_z)) {
             const int g4 = (wy & 1) ? 1 : 2, P = kThreads / (wy / g4);

@@ -39,6 +39,10 @@ inline hipError_t allow_lds(LdsOptIn& done, int bytes, K*... kernels) {
     const void* const list[] = {reinterpret_cast<const void*>(kernels)...};
     return allow_lds(done, bytes, list, (int)sizeof...(K));
 }
+// CU count of the device that is current at the first call (cached; 256 where the runtime does not say): what the plans size grids and
+// slot counts by (dgn_abi.hip)
+int n_cus();
+inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // n items over at most max_groups workgroups of at least min_per items each: `per` items per workgroup, `groups` workgroups that have
 // some (0 for n = 0: the callers that launch one regardless clamp it), and `bound` >= groups, the count a workspace of one slot per

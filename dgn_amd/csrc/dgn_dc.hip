@@ -8,17 +8,6 @@ namespace dgn {
 namespace dc {
 namespace {
 
-int n_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return cus;
-}
-
 bool check_classes(const char* fn, const DgnDegreeClasses* d) {
     if (!d || d->n_units < 0 || (d->n_units > 0 && (!d->vperm || !d->unit_class || !d->present || !d->scale))) {
         set_error("%s: incomplete DgnDegreeClasses", fn);
@@ -219,9 +208,9 @@ extern "C" int dgn_dc_wgrad(const DgnDegreeClasses* d, int32_t S, int32_t k, int
     const int64_t total = (int64_t)n * k;
     const dim3 fgrid((unsigned)((total + 63) / 64));
     switch (S) {
-        case 1: hipLaunchKernelGGL(dc_wgrad_finalize<1>, fgrid, dim3(64 * 16), 0, st, n, k, w.k_slice, w.kpad, w.ntn * 16, w.slots, p.run_mask, d->scale, p.part, g_wf, ldw, lay, hl); break;
-        case 2: hipLaunchKernelGGL(dc_wgrad_finalize<2>, fgrid, dim3(64 * 16), 0, st, n, k, w.k_slice, w.kpad, w.ntn * 16, w.slots, p.run_mask, d->scale, p.part, g_wf, ldw, lay, hl); break;
-        default: hipLaunchKernelGGL(dc_wgrad_finalize<3>, fgrid, dim3(64 * 16), 0, st, n, k, w.k_slice, w.kpad, w.ntn * 16, w.slots, p.run_mask, d->scale, p.part, g_wf, ldw, lay, hl); break;
+        case 1: hipLaunchKernelGGL(dc_wgrad_finalize<1>, fgrid, dim3(64 * wg::kSumWaves), 0, st, n, k, w.k_slice, w.kpad, w.ntn * 16, w.slots, p.run_mask, d->scale, p.part, g_wf, ldw, lay, hl); break;
+        case 2: hipLaunchKernelGGL(dc_wgrad_finalize<2>, fgrid, dim3(64 * wg::kSumWaves), 0, st, n, k, w.k_slice, w.kpad, w.ntn * 16, w.slots, p.run_mask, d->scale, p.part, g_wf, ldw, lay, hl); break;
+        default: hipLaunchKernelGGL(dc_wgrad_finalize<3>, fgrid, dim3(64 * wg::kSumWaves), 0, st, n, k, w.k_slice, w.kpad, w.ntn * 16, w.slots, p.run_mask, d->scale, p.part, g_wf, ldw, lay, hl); break;
     }
     DGN_HIP_CHECK(hipGetLastError());
     return DGN_OK;

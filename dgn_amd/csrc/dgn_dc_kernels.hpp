@@ -20,6 +20,7 @@
 #pragma once
 #include "dgn_common.hpp"
 #include "dgn_load4.hpp"
+#include "dgn_wgrad.hpp"
 
 #include <type_traits>
 
@@ -365,31 +366,10 @@ __device__ __forceinline__ void dc_wgrad_run(const DcWgradParams& p, float* lds_
     constexpr int half = 16 * (gs + xs);
     const int gq = (p.n + 3) >> 2, xq = (k_here + 3) >> 2, per_row = gq + xq, total = 16 * per_row;
     constexpr int kMaxItems = (16 * (NTN * 4 + KT * 32) + kWave * kWgWaves - 1) / (kWave * kWgWaves);
-    auto fetch = [&](Raw4 (&reg)[kMaxItems], int64_t strip) {
-#pragma unroll
-        for (int j = 0; j < kMaxItems; ++j) {
-            const int it = min(tid + j * kWave * kWgWaves, total - 1);
-            const int r = it / per_row, c = it - r * per_row;
-            const int nd = p.vperm[strip * 16 + r];
-            const int64_t row = max(nd, 0);
-            const bool is_g = c < gq;
-            reg[j] = load4_raw(is_g ? p.G + row * p.ldg : p.X + row * p.ldx, is_g ? 4 * c : k0 + 4 * (c - gq), is_g ? p.n : p.k, nd >= 0);
-        }
-    };
-    auto commit = [&](const Raw4 (&reg)[kMaxItems], int buf) {
-        float* Gb = lds_dc + buf * half;
-        float* Xb = Gb + 16 * gs;
-#pragma unroll
-        for (int j = 0; j < kMaxItems; ++j) {
-            const int it = tid + j * kWave * kWgWaves;
-            if (it < total) {
-                const int r = it / per_row, c = it - r * per_row;
-                const f4 v = load4_window(reg[j]);
-                if (c < gq) *reinterpret_cast<f4*>(Gb + r * gs + 4 * c) = v;
-                else *reinterpret_cast<f4*>(Xb + r * xs + 4 * (c - gq)) = v;
-            }
-        }
-    };
+    // a 16-row strip of G and of X (this k slice), rows gathered through vperm: wg::strip_fetch / strip_commit
+    const wg::Strip S{p.G, p.ldg, p.n, 0, p.X, p.ldx, p.k, k0, gq, per_row, total, false};
+    const wg::PermRows rows{p.vperm};
+    constexpr int kThreads = kWave * kWgWaves;
     const int ids = p.slots + kClasses;
     const int64_t s_begin = (int64_t)blockIdx.x * p.units_per_block * (kUnit / 16);
     const int64_t s_end = min(p.n_units, ((int64_t)blockIdx.x + 1) * p.units_per_block) * (kUnit / 16);
@@ -399,8 +379,8 @@ __device__ __forceinline__ void dc_wgrad_run(const DcWgradParams& p, float* lds_
     }
     uint32_t flushed = 0u;
     Raw4 sreg[kMaxItems];
-    fetch(sreg, s_begin);
-    commit(sreg, 0);
+    wg::strip_fetch<kThreads, false>(sreg, S, rows, s_begin);
+    wg::strip_commit<kThreads, false>(sreg, S, lds_dc, gs, lds_dc + 16 * gs, xs);
     __syncthreads();
     int buf = 0;
     int64_t strip = s_begin;
@@ -423,7 +403,7 @@ __device__ __forceinline__ void dc_wgrad_run(const DcWgradParams& p, float* lds_
             for (int b = 0; b < KTW; ++b) acc[a][b] = f4{0.f, 0.f, 0.f, 0.f};
         for (; strip < run_end; ++strip, buf ^= 1) {
             const bool more = strip + 1 < s_end;
-            if (more) fetch(sreg, strip + 1);
+            if (more) wg::strip_fetch<kThreads, false>(sreg, S, rows, strip + 1);
             const float* Gb = lds_dc + buf * half;
             const float* Xb = Gb + 16 * gs;
             // D[n][k] += G[m][n] X[m][k], the strip's rows are the reduction index: m = 4 s + g in the s-th instruction
@@ -439,7 +419,7 @@ __device__ __forceinline__ void dc_wgrad_run(const DcWgradParams& p, float* lds_
 #pragma unroll
                     for (int b = 0; b < KTW; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(gv[a], xv[b], acc[a][b], 0, 0, 0);
             }
-            if (more) commit(sreg, buf ^ 1);
+            if (more) wg::strip_commit<kThreads, false>(sreg, S, lds_dc + (buf ^ 1) * half, gs, lds_dc + (buf ^ 1) * half + 16 * gs, xs);
             __syncthreads();
         }
         float* out = p.part + ((int64_t)blockIdx.y * ids + blockIdx.x + cls) * (NTN * 16) * p.kpad;
@@ -471,13 +451,13 @@ __global__ __launch_bounds__(kWave * kWgWaves) void dc_wgrad(const DcWgradParams
 }
 
 // g_wf[(s n + o)][kk] = sum over the runs, in (workgroup, class) order, of scale[class][s] * part[run][o][kk]; a block covers 64
-// consecutive elements, its sixteen waves take every sixteenth workgroup, LDS joins them in wave order (bitwise reproducible).
+// consecutive elements, its sixteen waves take every sixteenth workgroup, wg::wave_join16 joins them in wave order (bitwise reproducible).
 // has_layout: the sums go straight into the reference's weight-gradient layout (DgnDcLayout) instead.
 template <int S>
-static __global__ __launch_bounds__(64 * 16) void dc_wgrad_finalize(int n, int k, int k_slice, int kpad, int npad, int slots, const uint32_t* __restrict__ run_mask,
+static __global__ __launch_bounds__(64 * wg::kSumWaves) void dc_wgrad_finalize(int n, int k, int k_slice, int kpad, int npad, int slots, const uint32_t* __restrict__ run_mask,
                                                                     const float* __restrict__ scale, const float* __restrict__ part,
                                                                     float* __restrict__ g_wf, int64_t ldw, const DgnDcLayout lay, int has_layout) {
-    __shared__ float red[S][16][64];
+    __shared__ float red[S][wg::kSumWaves][64];
     const int lane = threadIdx.x & 63, sg = threadIdx.x >> 6;
     const int64_t e = (int64_t)blockIdx.x * 64 + lane;
     const bool live = e < (int64_t)n * k;
@@ -488,7 +468,7 @@ static __global__ __launch_bounds__(64 * 16) void dc_wgrad_finalize(int n, int k
     float out[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) out[s] = 0.f;
-    for (int x = sg; x < slots; x += 16) {
+    for (int x = sg; x < slots; x += wg::kSumWaves) {
         uint32_t m = run_mask[x];
         while (m) {
             const int c = __builtin_ctz(m);
@@ -502,9 +482,7 @@ static __global__ __launch_bounds__(64 * 16) void dc_wgrad_finalize(int n, int k
     for (int s = 0; s < S; ++s) red[s][sg][lane] = out[s];
     __syncthreads();
     if (live && sg < S) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) v += red[sg][w][lane];
+        const float v = wg::wave_join16(red[sg], lane);
         if (has_layout) {
             const int64_t off = dc_ref_offset(lay, sg, o, kk);
             if (off >= 0) g_wf[off] = v;

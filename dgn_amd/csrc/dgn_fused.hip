@@ -15,17 +15,6 @@ int agg_backward_prepare(AggParams& p, const DgnGraph* g, const DgnAggSpec* spec
                          size_t ws_bytes, void* stream_, float** tab_part_out, const unsigned char* aux);
 namespace {
 
-int n_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return cus;
-}
-
 template <class C, class O>
 int launch_fwd(const FusedParams& p, size_t lds, hipStream_t st) {
     static LdsOptIn lds_ok{0};

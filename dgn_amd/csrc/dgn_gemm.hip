@@ -8,17 +8,6 @@ namespace dgn {
 namespace gemm {
 namespace {
 
-int n_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return cus;
-}
-
 template <int NT>
 hipError_t launch_gemm_nt(const GemmParams& p, dim3 grid, hipStream_t st, int wkn) {
     const size_t lds = (size_t)2 * NT * 16 * kKS * sizeof(float);
@@ -202,7 +191,7 @@ extern "C" int dgn_gemm_wgrad(int64_t n_rows, int32_t k, int32_t n, const float*
         DGN_HIP_CHECK(allow_lds(lds_ok, 160 * 1024, &tile_wgrad));
         hipLaunchKernelGGL(tile_wgrad, dim3(t.slots, t.n_blocks * t.k_blocks), dim3(kWave * kTwWaves), t.lds, st, p);
         const int64_t total = (int64_t)n * p.kk;
-        hipLaunchKernelGGL(tile_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * 16), 0, st, n, k, p.kk, t.slots, t.k_blocks,
+        hipLaunchKernelGGL(tile_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * wg::kSumWaves), 0, st, n, k, p.kk, t.slots, t.k_blocks,
                            t.nb_tiles * 32, t.kb_tiles * 32, p.part, dw, lddw, dbias);
         DGN_HIP_CHECK(hipGetLastError());
         return DGN_OK;

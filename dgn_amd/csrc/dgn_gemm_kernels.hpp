@@ -17,6 +17,7 @@
 
 #include "dgn_common.hpp"
 #include "dgn_load4.hpp"
+#include "dgn_wgrad.hpp"
 
 namespace dgn {
 namespace gemm {
@@ -308,40 +309,12 @@ __global__ __launch_bounds__(kWave * kWgWaves) void ts_gemm_wgrad(const WgradPar
     auto Gbuf = [&](int b) { return lds_g + b * half; };         // (pointer arithmetic, not a pointer table: a dynamically indexed
     auto Xbuf = [&](int b) { return lds_g + b * half + 16 * gs; };   //  array of pointers would live in scratch memory)
     const int64_t n_strips = (p.M + 15) / 16;
-    // a 16-row strip of G (all n columns) and of X (this k slice), zero beyond the matrices: fetched into registers before the
-    // current strip's MFMAs, committed to the other LDS buffer after them (see ts_gemm)
+    // a 16-row strip of G (all n columns, padded to whole tiles) and of X (this k slice): wg::strip_fetch / strip_commit
     constexpr int kMaxItems = (16 * (kWgWaves * 4 + KT * 4) + kWave * kWgWaves - 1) / (kWave * kWgWaves);
     const int gq = NTn * 4, xq = KT * 4;                         // float4's per staged row
-    auto fetch = [&](Raw4 (&reg)[kMaxItems], int64_t strip) {
-        const int64_t r0 = strip * 16;
-#pragma unroll
-        for (int j = 0; j < kMaxItems; ++j) {
-            const int it = min(tid + j * kWave * kWgWaves, 16 * (gq + xq) - 1);      // (surplus threads repeat the last piece; commit skips them)
-            const int r = it / (gq + xq), c = it - r * (gq + xq);
-            const int64_t row = min(r0 + r, p.M - 1);
-            const bool is_g = c < gq;
-            reg[j] = load4_raw(is_g ? p.G + row * p.ldg : p.X + row * p.ldx, is_g ? 4 * c : k0 + 4 * (c - gq), is_g ? p.n : p.k, r0 + r < p.M);
-            if (r0 + r >= p.M) reg[j].sh = 8;                              // (a row past the matrix: zeros, and no ones column either)
-        }
-    };
-    auto commit = [&](const Raw4 (&reg)[kMaxItems], int buf) {
-#pragma unroll
-        for (int j = 0; j < kMaxItems; ++j) {
-            const int it = tid + j * kWave * kWgWaves;
-            if (it < 16 * (gq + xq)) {
-                const int r = it / (gq + xq), c = it - r * (gq + xq);
-                f4 v = load4_window(reg[j]);
-                if (c < gq) *reinterpret_cast<f4*>(Gbuf(buf) + r * gs + 4 * c) = v;
-                else {
-                    if (p.kk > p.k && reg[j].sh < 8) {                  // (sh >= 8 marks a row past the matrix, see fetch)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = k0 + 4 * (c - gq) + e == p.k ? 1.f : v[e];      // column k of X := 1
-                    }
-                    *reinterpret_cast<f4*>(Xbuf(buf) + r * xs + 4 * (c - gq)) = v;
-                }
-            }
-        }
-    };
+    const wg::Strip S{p.G, p.ldg, p.n, 0, p.X, p.ldx, p.k, k0, gq, gq + xq, 16 * (gq + xq), p.kk > p.k};
+    const wg::ClampRows rows{p.M};
+    constexpr int kThreads = kWave * kWgWaves;
     f4 acc[KT];
 #pragma unroll
     for (int b = 0; b < KT; ++b) acc[b] = f4{0.f, 0.f, 0.f, 0.f};
@@ -350,13 +323,13 @@ __global__ __launch_bounds__(kWave * kWgWaves) void ts_gemm_wgrad(const WgradPar
     int buf = 0;
     Raw4 sreg[kMaxItems];
     if (strip < n_strips) {
-        fetch(sreg, strip);
-        commit(sreg, 0);
+        wg::strip_fetch<kThreads, true>(sreg, S, rows, strip);
+        wg::strip_commit<kThreads, true>(sreg, S, Gbuf(0), gs, Xbuf(0), xs);
     }
     __syncthreads();
     for (; strip < n_strips; strip += gridDim.x, buf ^= 1) {
         const bool more = strip + gridDim.x < n_strips;
-        if (more) fetch(sreg, strip + gridDim.x);
+        if (more) wg::strip_fetch<kThreads, true>(sreg, S, rows, strip + gridDim.x);
         if (has_tile) {
             // D[n][k] += G[m][n] X[m][k], the strip's rows are the reduction index: m = 4 s + g in the s-th instruction
 #pragma unroll
@@ -367,7 +340,7 @@ __global__ __launch_bounds__(kWave * kWgWaves) void ts_gemm_wgrad(const WgradPar
                 for (int b = 0; b < KT; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(gv, xr[16 * b], acc[b], 0, 0, 0);
             }
         }
-        if (more) commit(sreg, buf ^ 1);
+        if (more) wg::strip_commit<kThreads, true>(sreg, S, Gbuf(buf ^ 1), gs, Xbuf(buf ^ 1), xs);
         __syncthreads();
     }
     // lane holds D[n = 16 wave + 4 g + r][k = 16 b + i16]
@@ -442,38 +415,9 @@ struct TwBlock {
     int n0, k0, n_here, k_here, gs, xs, half, gq, per_row, total;
 };
 
-// a 16-row strip of G's and X's column blocks, zero beyond the matrices, column k of X := 1 (the bias gradient's ones column)
-__device__ __forceinline__ void tw_fetch(Raw4 (&reg)[kTwItems], const TileWgParams& p, const TwBlock& B, int64_t strip, int tid) {
-    const int64_t r0 = strip * kTwRows;
-#pragma unroll
-    for (int j = 0; j < kTwItems; ++j) {
-        const int it = min(tid + j * kWave * kTwWaves, B.total - 1);          // (surplus threads repeat the last piece; commit skips them)
-        const int r = it / B.per_row, c = it - r * B.per_row;
-        const int64_t row = min(r0 + r, p.M - 1);
-        const bool is_g = c < B.gq;
-        // (absolute columns against the whole row's width: always >= 4 columns to clamp into; X: its real columns, the ones column is set at commit)
-        reg[j] = load4_raw(is_g ? p.G + row * p.ldg : p.X + row * p.ldx, (is_g ? B.n0 : B.k0) + 4 * (is_g ? c : c - B.gq), is_g ? p.n : p.k, r0 + r < p.M);
-    }
-}
-__device__ __forceinline__ void tw_commit(const Raw4 (&reg)[kTwItems], float* Gb, const TileWgParams& p, const TwBlock& B, int64_t strip, int tid) {
-    float* Xb = Gb + kTwRows * B.gs;
-#pragma unroll
-    for (int j = 0; j < kTwItems; ++j) {
-        const int it = tid + j * kWave * kTwWaves;
-        if (it < B.total) {
-            const int r = it / B.per_row, c = it - r * B.per_row;
-            f4 v = load4_window(reg[j]);
-            if (c < B.gq) *reinterpret_cast<f4*>(Gb + r * B.gs + 4 * c) = v;
-            else {
-                const int gcol = B.k0 + 4 * (c - B.gq);
-                if (p.kk > p.k && strip * kTwRows + r < p.M) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = gcol + e == p.k ? 1.f : v[e];        // column k of X := 1 on the rows that exist
-                }
-                *reinterpret_cast<f4*>(Xb + r * B.xs + 4 * (c - B.gq)) = v;
-            }
-        }
-    }
+// a 16-row strip of G's and X's column blocks (wg::strip_fetch / strip_commit)
+__device__ __forceinline__ wg::Strip tw_strip(const TileWgParams& p, const TwBlock& B) {
+    return wg::Strip{p.G, p.ldg, p.n, B.n0, p.X, p.ldx, p.k, B.k0, B.gq, B.per_row, B.total, p.kk > p.k};
 }
 
 // The strip loop of a wave that owns NTc x KTc tiles (n tiles from a0, k tiles from b0): counts as template arguments -- MFMAs under
@@ -491,15 +435,18 @@ __device__ __forceinline__ void tw_run(const TileWgParams& p, const TwBlock& B, 
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
     const int64_t n_strips = (p.M + kTwRows - 1) / kTwRows;
     Raw4 sreg[kTwItems];
+    const wg::Strip S = tw_strip(p, B);
+    const wg::ClampRows rows{p.M};
+    constexpr int kThreads = kWave * kTwWaves;
     if ((int64_t)blockIdx.x < n_strips) {
-        tw_fetch(sreg, p, B, blockIdx.x, tid);
-        tw_commit(sreg, lds, p, B, blockIdx.x, tid);
+        wg::strip_fetch<kThreads, true>(sreg, S, rows, blockIdx.x);
+        wg::strip_commit<kThreads, true>(sreg, S, lds, B.gs, lds + kTwRows * B.gs, B.xs);
     }
     __syncthreads();
     int buf = 0;
     for (int64_t strip = blockIdx.x; strip < n_strips; strip += gridDim.x, buf ^= 1) {
         const bool more = strip + gridDim.x < n_strips;
-        if (more) tw_fetch(sreg, p, B, strip + gridDim.x, tid);
+        if (more) wg::strip_fetch<kThreads, true>(sreg, S, rows, strip + gridDim.x);
         const float* Gb = lds + buf * B.half + 32 * a0 + i32;
         const float* Xb = lds + buf * B.half + kTwRows * B.gs + 32 * b0 + i32;
         // D[n][k] += G[m][n] X[m][k]: the pair of rows m = 2 s + hi is the reduction index of the s-th instruction
@@ -516,7 +463,7 @@ __device__ __forceinline__ void tw_run(const TileWgParams& p, const TwBlock& B, 
 #pragma unroll
                 for (int b = 0; b < KTc; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(gv[a], xv[b], acc[a][b], 0, 0, 0);
         }
-        if (more) tw_commit(sreg, lds + (buf ^ 1) * B.half, p, B, strip + gridDim.x, tid);
+        if (more) wg::strip_commit<kThreads, true>(sreg, S, lds + (buf ^ 1) * B.half, B.gs, lds + (buf ^ 1) * B.half + kTwRows * B.gs, B.xs);
         __syncthreads();
     }
     // lane holds D[32 a + (r & 3) + 8 (r >> 2) + 4 hi][32 b + i32] of its tiles: the workgroup's partial block goes to its slot
@@ -561,35 +508,22 @@ __global__ __launch_bounds__(kWave * kTwWaves) void tile_wgrad(const TileWgParam
     }
 }
 
-// dW[n][k] (and dbias[n] = column k of the padded product) = the slot sums in slot order; a block covers 64 consecutive elements, its
-// sixteen waves take every sixteenth slot, LDS joins them (as dgn_linear's finalize)
-static __global__ __launch_bounds__(64 * 16) void tile_wgrad_finalize(int n, int k, int kk, int slots, int k_blocks, int nbc, int kbc,
-                                                                      const float* __restrict__ part, float* __restrict__ dW, int64_t lddw,
-                                                                      float* __restrict__ dbias) {
-    __shared__ float red[16][64];
-    const int lane = threadIdx.x & 63, sg = threadIdx.x >> 6;
-    const int64_t e = (int64_t)blockIdx.x * 64 + lane;
+// dW[n][k] (and dbias[n] = column k of the padded product) = the slot sums in wg::slot_sum16's fixed order
+static __global__ __launch_bounds__(64 * wg::kSumWaves) void tile_wgrad_finalize(int n, int k, int kk, int slots, int k_blocks, int nbc, int kbc,
+                                                                                 const float* __restrict__ part, float* __restrict__ dW, int64_t lddw,
+                                                                                 float* __restrict__ dbias) {
+    __shared__ float red[wg::kSumWaves][64];
+    const int64_t e = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     const bool live = e < (int64_t)n * kk;
     int r = 0, c = 0;
-    float s0 = 0.f, s1 = 0.f;
     if (live) {
         r = (int)(e / kk);
         c = (int)(e - (int64_t)r * kk);
-        const int bn = r / nbc, bk = c / kbc;
-        const float* src = part + (int64_t)(bn * k_blocks + bk) * slots * nbc * kbc + (int64_t)(r - bn * nbc) * kbc + (c - bk * kbc);
-        int q = sg;
-        for (; q + 16 < slots; q += 32) {
-            s0 += src[(int64_t)q * nbc * kbc];
-            s1 += src[(int64_t)(q + 16) * nbc * kbc];
-        }
-        if (q < slots) s0 += src[(int64_t)q * nbc * kbc];
     }
-    red[sg][lane] = s0 + s1;
-    __syncthreads();
-    if (live && sg == 0) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) v += red[w][lane];
+    const int bn = r / nbc, bk = c / kbc;
+    const float v = wg::slot_sum16(part + (int64_t)(bn * k_blocks + bk) * slots * nbc * kbc + (int64_t)(r - bn * nbc) * kbc + (c - bk * kbc),
+                                   (int64_t)nbc * kbc, slots, live, red);
+    if (live && threadIdx.x < 64) {
         if (c < k) dW[(int64_t)r * lddw + c] = v;
         else if (dbias) dbias[r] = v;
     }

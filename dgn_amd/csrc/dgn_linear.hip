@@ -10,19 +10,7 @@ hipError_t launch_linear_plain(int nt, int kb, const LinParams& p, int threads, 
 }
 
 namespace {
-int n_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return cus;
-}
-
 bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
 }  // namespace
 }  // namespace lin
 }  // namespace dgn
@@ -132,7 +120,6 @@ extern "C" int dgn_linear_forward_add(int64_t n_rows, int32_t k, int32_t n, cons
     if (n_rows < 0 || !dgn_linear_add_supported(k, n)) { set_error("%s: widths outside the supported set (k=%d n=%d)", fn, k, n); return -1; }
     if (n_rows == 0) return 0;
     if (!a || !w || !c || !add1) { set_error("%s: null operand", fn); return -1; }
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     if (!aligned8(a) || !al16(c) || !al16(add1) || (add2 && !al16(add2))) { set_error("%s: a must be 8-byte, c / add1 / add2 16-byte aligned (dense rows)", fn); return -1; }
     LinParams p{};
     p.M = n_rows; p.k = k; p.n = n; p.T = 1;
@@ -149,7 +136,6 @@ extern "C" int dgn_linear_forward_bn_act(int64_t n_rows, int32_t k, int32_t n, c
     if (n_rows < 0 || !dgn_linear_add_supported(k, n)) { set_error("%s: widths outside the supported set (k=%d n=%d)", fn, k, n); return -1; }
     if (n_rows == 0) return 0;
     if (!a || !w || !z_out || !out || !bn_mean || !bn_invstd) { set_error("%s: null operand", fn); return -1; }
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     if (!aligned8(a) || !al16(z_out) || !al16(out) || (residual && !al16(residual))) { set_error("%s: a must be 8-byte, z_out / out / residual 16-byte aligned", fn); return -1; }
     LinParams p{};
     p.M = n_rows; p.k = k; p.n = n; p.T = 1;
@@ -170,7 +156,7 @@ extern "C" int dgn_linear_forward_act(int64_t n_rows, int32_t k, int32_t n, cons
     if (n_rows < 0 || !dgn_linear_act_supported(k, n)) { set_error("%s: need even k, n in [2, 160] (k=%d n=%d)", fn, k, n); return -1; }
     if (n_rows == 0) return 0;
     if (!g || !z || !w || !c) { set_error("%s: null operand", fn); return -1; }
-    if (!aligned8(g) || !aligned8(z) || !aligned8(c) || (gz_out && (reinterpret_cast<uintptr_t>(gz_out) & 15))) { set_error("%s: operands must be 8-byte aligned (dense rows), gz_out 16-byte aligned", fn); return -1; }
+    if (!aligned8(g) || !aligned8(z) || !aligned8(c) || (gz_out && !al16(gz_out))) { set_error("%s: operands must be 8-byte aligned (dense rows), gz_out 16-byte aligned", fn); return -1; }
     LinParams p{};
     p.M = n_rows; p.k = k; p.n = n; p.T = 1;
     p.A = g; p.W = w; p.ldw = ldw; p.w_kn = w_is_kn;
@@ -188,7 +174,6 @@ extern "C" int dgn_linear_forward_bn_act_mask(int64_t n_rows, int32_t k, int32_t
     if (n_rows < 0 || !dgn_linear_add_supported(k, n)) { set_error("%s: widths outside the supported set (k=%d n=%d)", fn, k, n); return -1; }
     if (n_rows == 0) return 0;
     if (!a || !w || !zmask_out || !out || !bn_mean || !bn_invstd) { set_error("%s: null operand", fn); return -1; }
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     if (!aligned8(a) || !al16(zmask_out) || !al16(out) || (residual && !al16(residual))) { set_error("%s: a must be 8-byte, zmask_out / out / residual 16-byte aligned", fn); return -1; }
     LinParams p{};
     p.M = n_rows; p.k = k; p.n = n; p.T = 1;
@@ -205,7 +190,7 @@ extern "C" int dgn_linear_forward_act_mask(int64_t n_rows, int32_t k, int32_t n,
     if (n_rows < 0 || !dgn_linear_act_supported(k, n)) { set_error("%s: need even k, n in [2, 160] (k=%d n=%d)", fn, k, n); return -1; }
     if (n_rows == 0) return 0;
     if (!g || !zmask || !w || !c) { set_error("%s: null operand", fn); return -1; }
-    if (!aligned8(g) || (reinterpret_cast<uintptr_t>(zmask) & 1) || !aligned8(c) || (gz_out && (reinterpret_cast<uintptr_t>(gz_out) & 15))) { set_error("%s: g / c must be 8-byte aligned (dense rows), zmask 2-byte, gz_out 16-byte aligned", fn); return -1; }
+    if (!aligned8(g) || (reinterpret_cast<uintptr_t>(zmask) & 1) || !aligned8(c) || (gz_out && !al16(gz_out))) { set_error("%s: g / c must be 8-byte aligned (dense rows), zmask 2-byte, gz_out 16-byte aligned", fn); return -1; }
     LinParams p{};
     p.M = n_rows; p.k = k; p.n = n; p.T = 1;
     p.A = g; p.W = w; p.ldw = ldw; p.w_kn = w_is_kn;
@@ -229,7 +214,6 @@ extern "C" int dgn_linear_forward_act_mask_bnb(int64_t n_rows, int32_t k, int32_
     }
     if (n_rows == 0) return 0;
     if (!g || !zmask || !w || !y || !bn_mean || !bn_invstd || !sums || !gz) { set_error("%s: null operand", fn); return -1; }
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     if (!aligned8(g) || (reinterpret_cast<uintptr_t>(zmask) & 1) || !al16(y) || !aligned8(gz) || (stride_gz & 1)) {
         set_error("%s: g 8-byte, zmask 2-byte, y 16-byte, gz 8-byte aligned (dense rows, even tower stride)", fn);
         return -1;
@@ -320,7 +304,7 @@ static int launch_wgrad(const char* fn, WgParams& p, float* dw, int64_t lddw, in
     const hipError_t e = p.ex.gy ? launch_wgrad_expand(NT, KT, p, lds, st) : (p.g_mask ? launch_wgrad_gmask(NT, KT, p, lds, st) : launch_wgrad_plain(NT, KT, p, lds, st));
     DGN_HIP_CHECK(e);
     const int64_t total = (int64_t)batch * n * (dbias ? k + 1 : k);
-    hipLaunchKernelGGL(ts_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * kFinWaves), 0, st, batch, n, k, p.groups,
+    hipLaunchKernelGGL(ts_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * wg::kSumWaves), 0, st, batch, n, k, p.groups,
                        NT * 16, KT * 16, p.part, dw, lddw, stride_dw, dbias, stride_dbias, dbias ? pick : nullptr, pick_off, pick_w);
     DGN_HIP_CHECK(hipGetLastError());
     return 0;
@@ -380,7 +364,7 @@ extern "C" int dgn_linear_wgrad_bn_act_mask(int64_t n_rows, int32_t k, int32_t n
     if (n_rows < 0 || !dgn_linear_supported(k, n, 1)) { set_error("%s: need even k, n in [2, 160] and at most 45 tiles (k=%d n=%d)", fn, k, n); return -1; }
     if (!dw) { set_error("%s: null output", fn); return -1; }
     if (n_rows == 0) return zero_wgrad(dw, lddw, 0, dbias, 0, k, n, 1, static_cast<hipStream_t>(stream));
-    if (!g || !zmask || !x || !bn_mean || !bn_invstd || !aligned8(g) || !aligned8(x) || (reinterpret_cast<uintptr_t>(zmask) & 15)) {
+    if (!g || !zmask || !x || !bn_mean || !bn_invstd || !aligned8(g) || !aligned8(x) || !al16(zmask)) {
         set_error("%s: null or misaligned operand (g, x 8-byte; zmask 16-byte: its strips travel as 16-byte direct-to-LDS pieces)", fn);
         return -1;
     }

@@ -308,23 +308,8 @@ __global__ __launch_bounds__(256, bd_wg_waves_per_simd(T, (FI + 15) / 16)) void 
             __builtin_amdgcn_sched_barrier(0);        // (one row quartet's operands at a time: hoisting all four costs the second wave per SIMD)
         }
     }
-    // lane holds tile (t, j, a, b) entries [4 mq + r][i16]
-    __syncthreads();
-    float* red = lds;                                // [NTL][16][16]
-    for (int w = 0; w < n_waves; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int q = 0; q < NTL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float* d = red + q * 256 + (4 * mq + r) * 16 + i16;
-                    *d = w == 0 ? acc[q][r] : *d + acc[q][r];
-                }
-        }
-        __syncthreads();
-    }
-    float* out = p.part + (int64_t)blockIdx.x * NTL * 256;
-    for (int i = tid; i < NTL * 64; i += blockDim.x) reinterpret_cast<f4*>(out)[i] = reinterpret_cast<const f4*>(red)[i];
+    // lane holds tile (t, j, a, b) entries [4 mq + r][i16]: the workgroup's block [NTL][16][16] is folded over the strips' LDS
+    wg::wave_fold<NTL * 256>(lds, p.part, blockIdx.x, acc, [&](int q, int r) { return q * 256 + (4 * mq + r) * 16 + i16; });
 }
 
 // Round 6: the input gradient AND the weight gradient of the block-diagonal product in ONE pass over g = d(P|Q): bd_backward_input and
@@ -452,76 +437,35 @@ __global__ __launch_bounds__(512) void bd_backward_both(BdParams p) {
         out_strip = strip;
     }
     if (out_strip >= 0) store_out();
-    // the workgroup's waves add their weight-gradient tiles up in LDS in wave order (bd_wgrad's epilogue)
-    __syncthreads();
-    float* red = lds;                                // [NTW][16][16]
-    for (int w = 0; w < n_waves; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int q = 0; q < NTW; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float* d = red + q * 256 + (4 * g + r) * 16 + m;
-                    *d = w == 0 ? accw[q][r] : *d + accw[q][r];
-                }
-        }
-        __syncthreads();
-    }
-    float* out = p.part + (int64_t)blockIdx.x * NTW * 256;
-    for (int i = tid; i < NTW * 64; i += blockDim.x) reinterpret_cast<f4*>(out)[i] = reinterpret_cast<const f4*>(red)[i];
+    // the workgroup's weight-gradient block [NTW][16][16], folded over the (now dead) weights and strips
+    wg::wave_fold<NTW * 256>(lds, p.part, blockIdx.x, accw, [&](int q, int r) { return q * 256 + (4 * g + r) * 16 + m; });
 }
 
-// dW (dense [2 Fm][lddw]: diagonal blocks = the slot sums in a fixed order, everything else zero) and dbias [2 Fm]
-static __global__ __launch_bounds__(64 * kFinWaves) void bd_wgrad_finalize(int T, int fi, int FB, int slots, const float* __restrict__ part,
-                                                                           float* __restrict__ dW, int64_t lddw, float* __restrict__ dbias) {
-    __shared__ float red[kFinWaves][64];
+// dW (dense [2 Fm][lddw]: diagonal blocks = the slot sums in wg::slot_sum16's fixed order, everything else zero) and dbias [2 Fm]
+static __global__ __launch_bounds__(64 * wg::kSumWaves) void bd_wgrad_finalize(int T, int fi, int FB, int slots, const float* __restrict__ part,
+                                                                               float* __restrict__ dW, int64_t lddw, float* __restrict__ dbias) {
+    __shared__ float red[wg::kSumWaves][64];
     const int Fm = T * fi, kk = Fm + 1, ntl = 2 * T * FB * FB;
-    const int lane = threadIdx.x & 63, sg = threadIdx.x >> 6;
-    const int64_t e = (int64_t)blockIdx.x * 64 + lane;
+    const int64_t e = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     const bool live = e < (int64_t)2 * Fm * kk;
-    int r = 0, c = 0;
+    int r = 0, c = 0, off = 0;
     bool diag = false;
-    float s0 = 0.f, s1 = 0.f;
     if (live) {
         r = (int)(e / kk);
         c = (int)(e - (int64_t)r * kk);
         const int j = r / Fm, rr = r - j * Fm, t = rr / fi, a = rr - t * fi;
         const int b = c == Fm ? fi : c - t * fi;                                   // local column; f_in = the ones column
         diag = c == Fm || (c >= t * fi && c < (t + 1) * fi);
-        if (diag) {
-            const int tile = ((t * 2 + j) * FB + (a >> 4)) * FB + (b >> 4);
-            const float* src = part + tile * 256 + (a & 15) * 16 + (b & 15);
-            int q = sg;
-            for (; q + kFinWaves < slots; q += 2 * kFinWaves) {
-                s0 += src[(int64_t)q * ntl * 256];
-                s1 += src[(int64_t)(q + kFinWaves) * ntl * 256];
-            }
-            if (q < slots) s0 += src[(int64_t)q * ntl * 256];
-        }
+        if (diag) off = (((t * 2 + j) * FB + (a >> 4)) * FB + (b >> 4)) * 256 + (a & 15) * 16 + (b & 15);
     }
-    red[sg][lane] = s0 + s1;
-    __syncthreads();
-    if (live && sg == 0) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < kFinWaves; ++w) v += red[w][lane];
-        if (c < Fm) dW[(int64_t)r * lddw + c] = diag ? v : 0.f;
+    const float v = wg::slot_sum16(part + off, (int64_t)ntl * 256, slots, diag, red);       // (off the diagonal: nothing read, zero)
+    if (live && threadIdx.x < 64) {
+        if (c < Fm) dW[(int64_t)r * lddw + c] = v;
         else if (dbias) dbias[r] = v;
     }
 }
 
 namespace {
-int bd_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return cus;
-}
-
 // The instantiated (towers, f_in) shapes -- f_in is a template argument so that every tower's LDS offsets are instruction immediates
 // (as a runtime value they cost one address register per tower and operand: the kernels then spill).  The list: five towers (the
 // reference's default, nets/dgn_layer.py:330) over the even per-tower widths up to 30; hidden 70 = 5 x 14 is BASELINE configs[1].
@@ -564,11 +508,9 @@ hipError_t bd_launch(int which, const BdParams& p, int threads, size_t lds, hipS
 
 int bd_max_threads(int which, int T, int FB) { return which == kBdFwd ? bd_fwd_threads(T, FB) : bd_bwd_threads(T, FB); }
 
-bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 int bd_wgrad_groups(int64_t n_rows) {
     const int64_t n_strips = (n_rows + kStrip - 1) / kStrip;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(2 * bd_cus(), (n_strips + 3) / 4));
+    return (int)std::max<int64_t>(1, std::min<int64_t>(2 * n_cus(), (n_strips + 3) / 4));
 }
 
 // forward / input gradient: persistent workgroups, as many waves per CU as LDS and registers allow
@@ -589,7 +531,7 @@ int bd_launch_stream(const char* fn, int which, BdParams& p, void* stream) {
     if (!waves) { set_error("%s: operands do not fit in LDS", fn); return -1; }
     const size_t lds = (w_floats + waves * wave_floats) * 4;
     const int64_t n_strips = (p.M + kStrip - 1) / kStrip;
-    p.groups = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)bd_cus() * per_cu, (n_strips + waves - 1) / waves));
+    p.groups = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)n_cus() * per_cu, (n_strips + waves - 1) / waves));
     DGN_HIP_CHECK(bd_launch(which, p, waves * 64, lds, static_cast<hipStream_t>(stream)));
     return 0;
 }
@@ -656,7 +598,7 @@ extern "C" int dgn_linear_bd_wgrad(int64_t n_rows, int32_t n_towers, int32_t f_i
     const size_t lds = std::max((size_t)4 * (strip_floats(2 * Fm) + strip_floats(Fm)), (size_t)ntl * 256) * 4;
     DGN_HIP_CHECK(bd_launch(kBdWg, p, 256, lds, st));
     const int64_t total = (int64_t)2 * Fm * (Fm + 1);
-    hipLaunchKernelGGL(bd_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * kFinWaves), 0, st, n_towers, f_in, FB, p.groups, p.part, dw, lddw,
+    hipLaunchKernelGGL(bd_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * wg::kSumWaves), 0, st, n_towers, f_in, FB, p.groups, p.part, dw, lddw,
                        dbias);
     DGN_HIP_CHECK(hipGetLastError());
     return DGN_OK;
@@ -691,11 +633,11 @@ int bd_backward_both_launch(int64_t n_rows, int32_t n_towers, int32_t f_in, cons
     BdParams p{};
     p.M = n_rows; p.T = n_towers; p.fi = f_in; p.A = g; p.X = x; p.W = w; p.ldw = ldw; p.C = g_h; p.add1 = add1; p.add2 = add2;
     p.part = static_cast<float*>(ws);
-    p.groups = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(bd_cus(), bd_wgrad_groups(n_rows)), (n_strips + waves - 1) / waves));
+    p.groups = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_cus(), bd_wgrad_groups(n_rows)), (n_strips + waves - 1) / waves));
     hipStream_t st = static_cast<hipStream_t>(stream);
     DGN_HIP_CHECK(bd_launch(kBdBoth, p, waves * 64, lds, st));
     const int64_t total = (int64_t)2 * Fm * (Fm + 1);
-    hipLaunchKernelGGL(bd_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * kFinWaves), 0, st, n_towers, f_in, FB, p.groups, p.part, dw, lddw,
+    hipLaunchKernelGGL(bd_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * wg::kSumWaves), 0, st, n_towers, f_in, FB, p.groups, p.part, dw, lddw,
                        dbias);
     DGN_HIP_CHECK(hipGetLastError());
     return DGN_OK;

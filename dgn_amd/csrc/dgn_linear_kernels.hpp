@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "dgn_common.hpp"
+#include "dgn_wgrad.hpp"
 
 namespace dgn {
 namespace lin {
@@ -713,11 +714,9 @@ __global__ __launch_bounds__(256, wgrad_min_blocks(NT, KT, GMASK)) void ts_wgrad
             buf ^= 1;
         }
     };
-    f4 acc[NT][KT];
+    f4 acc[NT * KT];
 #pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-        for (int b = 0; b < KT; ++b) acc[a][b] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < NT * KT; ++q) acc[q] = f4{0.f, 0.f, 0.f, 0.f};
 
     const int i16 = lane & 15, mq = lane >> 4;
     if (first < n_strips) {
@@ -762,66 +761,34 @@ __global__ __launch_bounds__(256, wgrad_min_blocks(NT, KT, GMASK)) void ts_wgrad
 #pragma unroll
             for (int a = 0; a < NT; ++a)
 #pragma unroll
-                for (int b = 0; b < KT; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(gv[a], xv[b], acc[a][b], 0, 0, 0);
+                for (int b = 0; b < KT; ++b) acc[a * KT + b] = __builtin_amdgcn_mfma_f32_16x16x4f32(gv[a], xv[b], acc[a * KT + b], 0, 0, 0);
         }
     }
-    // lane holds D[n = 16a + 4*mq + r][k = 16b + i16]: the workgroup's waves add up in LDS in wave order, one slot
-    // per workgroup goes to memory
-    __syncthreads();
-    float* red = lds;                                // [NT*16][KT*16], reuses the strips
-    for (int w = 0; w < n_waves; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int a = 0; a < NT; ++a)
-#pragma unroll
-                for (int b = 0; b < KT; ++b)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float* d = red + (16 * a + 4 * mq + r) * (KT * 16) + 16 * b + i16;
-                        *d = w == 0 ? acc[a][b][r] : *d + acc[a][b][r];
-                    }
-        }
-        __syncthreads();
-    }
-    float* out = p.part + ((int64_t)t * p.groups + grp) * (NT * 16) * (KT * 16);
-    for (int i = tid; i < NT * 16 * KT * 16 / 4; i += blockDim.x) reinterpret_cast<f4*>(out)[i] = reinterpret_cast<const f4*>(red)[i];
+    // lane holds D[n = 16a + 4*mq + r][k = 16b + i16] of tile a KT + b: the workgroup's block [NT*16][KT*16] is folded over the strips' LDS
+    wg::wave_fold<NT * 16 * KT * 16>(lds, p.part, (int64_t)t * p.groups + grp, acc,
+                                     [&](int q, int r) { return (16 * (q / KT) + 4 * mq + r) * (KT * 16) + 16 * (q % KT) + i16; });
 }
 
-// dW[t][n][k] = sum over the workgroup slots in a fixed order (bitwise reproducible): a block covers 64 consecutive
-// elements, its sixteen waves take every sixteenth slot (all loads of a lane in flight together), LDS joins them
-constexpr int kFinWaves = 16;
-static __global__ __launch_bounds__(64 * kFinWaves) void ts_wgrad_finalize(int T, int n, int k, int slots, int npad, int kpad,
+// dW[t][n][k] = the slot sums in wg::slot_sum16's fixed order (bitwise reproducible)
+static __global__ __launch_bounds__(64 * wg::kSumWaves) void ts_wgrad_finalize(int T, int n, int k, int slots, int npad, int kpad,
                                                          const float* __restrict__ part, float* __restrict__ dW,
                                                          int64_t lddw, int64_t sdW, float* __restrict__ dbias, int64_t sdb,
                                                          float* __restrict__ pick = nullptr, int pick_off = 0, int pick_w = 0) {
     // (pick: rows [pick_off, pick_off + pick_w) of every batch entry's bias gradient also go, densely, to pick[t * pick_w + ...]: the identity
     //  scaler's block of the expanded gradient's column sums IS the posttrans bias gradient -- no launch of its own)
-    __shared__ float red[kFinWaves][64];
+    __shared__ float red[wg::kSumWaves][64];
     const int kk = dbias ? k + 1 : k;                // with the ones column: k + 1 columns per row, the last one is the bias gradient
-    const int lane = threadIdx.x & 63, sg = threadIdx.x >> 6;
-    const int64_t e = (int64_t)blockIdx.x * 64 + lane;
+    const int64_t e = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     const bool live = e < (int64_t)T * n * kk;
     int t = 0, r = 0, c = 0;
-    float s0 = 0.f, s1 = 0.f;
     if (live) {
         t = (int)(e / ((int64_t)n * kk));
         const int rem = (int)(e - (int64_t)t * n * kk);
         r = rem / kk;
         c = rem - r * kk;
-        const float* src = part + (int64_t)t * slots * npad * kpad + (int64_t)r * kpad + c;
-        int q = sg;
-        for (; q + kFinWaves < slots; q += 2 * kFinWaves) {
-            s0 += src[(int64_t)q * npad * kpad];
-            s1 += src[(int64_t)(q + kFinWaves) * npad * kpad];
-        }
-        if (q < slots) s0 += src[(int64_t)q * npad * kpad];
     }
-    red[sg][lane] = s0 + s1;
-    __syncthreads();
-    if (live && sg == 0) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < kFinWaves; ++w) v += red[w][lane];
+    const float v = wg::slot_sum16(part + (int64_t)t * slots * npad * kpad + (int64_t)r * kpad + c, (int64_t)npad * kpad, slots, live, red);
+    if (live && threadIdx.x < 64) {
         if (c < k) dW[(int64_t)t * sdW + (int64_t)r * lddw + c] = v;
         else {
             dbias[(int64_t)t * sdb + r] = v;
