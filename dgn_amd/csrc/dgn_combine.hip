@@ -115,6 +115,14 @@ struct Cursor {
 // backward slab height: what the tile budget allows, at most 32 rows
 int bwd_slab_rows(int wy) { return std::max(1, std::min(32, kTileFloats / wy)); }
 
+// combine_bwd's dynamic LDS: the floats of its four regions, one behind the other (see the kernel); c_t only with BatchNorm
+struct BwdLayout {
+    int rows, wy, S, bn;
+    __host__ __device__ size_t g_t() const { return (size_t)rows * wy; }
+    __host__ __device__ size_t s_t() const { return (size_t)rows * S; }
+    size_t bytes() const { return (g_t() + s_t() + wy + (bn ? 6 * (size_t)wy : 0)) * sizeof(float); }      // (b_t [wy], c_t [6][wy])
+};
+
 // Backward: g_z[t][n][s*fo+o] = row_scale[n] * scale[n,s] * g_y[n, t*fo+o].  A workgroup walks slabs b, b + G, ...;
 // each slab of row_scale * g_y is staged in LDS so that the g_z stores of one tower are one contiguous run (a
 // thread-per-column layout wrote 168-byte pieces).  The bias gradient sum_n row_scale[n] * g_y[n, :] is kept per
@@ -128,9 +136,10 @@ __global__ __launch_bounds__(kThreads) void combine_bwd(int64_t n_nodes, int row
                                                         int has_bn) {
     extern __shared__ float lds[];
     const int zw = S * fo, wy = T * fo, G = (int)gridDim.x;
+    const BwdLayout L{rows_per_block, wy, S, has_bn};
     float* g_t = lds;                                // [rows][wy]   row_scale * g_y
-    float* s_t = g_t + (size_t)rows_per_block * wy;  // [rows][S]
-    float* b_t = s_t + (size_t)rows_per_block * S;   // [wy]         bias-gradient partial of this workgroup
+    float* s_t = g_t + L.g_t();                      // [rows][S]
+    float* b_t = s_t + L.s_t();                      // [wy]         bias-gradient partial of this workgroup
     float* c_t = b_t + wy;                           // [6][wy]      BatchNorm-backward column constants (fused form)
     // rows >= n_valid (DgnBnGrad.n_valid: padding rows of a batch held at a fixed capacity) took no part in the batch statistics and
     // get a zero gradient
@@ -405,7 +414,7 @@ int dgn::scale_combine_backward_impl(int64_t n_nodes, int32_t T, int32_t S, int3
         return DGN_ERR_WORKSPACE;
     }
     const int rows = bwd_slab_rows(wy), G = bwd_groups(n_nodes, rows);
-    const size_t lds = ((size_t)rows * wy + (size_t)rows * S + wy + (bn ? 6 * (size_t)wy : 0)) * sizeof(float);
+    const size_t lds = BwdLayout{rows, wy, S, bn != nullptr}.bytes();
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* part = g_bias ? static_cast<float*>(ws) : nullptr;
     {   // one tower, no scaler table, dense rows of a width that is no multiple of four, 16-byte aligned: flat 16-byte chunks

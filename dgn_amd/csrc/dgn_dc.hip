@@ -31,7 +31,7 @@ WgPlan wgrad_plan(int64_t n_units, int k, int n) {
     const int64_t want = std::max<int64_t>(1, n_cus() / w.k_slices);
     w.units_per_block = std::max<int64_t>(1, (n_units + want - 1) / want);
     w.slots = (int)std::max<int64_t>(1, (n_units + w.units_per_block - 1) / w.units_per_block);
-    w.lds = (size_t)2 * 16 * ((w.ntn * 16 + 4) + (w.kt * 128 + 4)) * sizeof(float);
+    w.lds = wgrad_bufs(w.ntn, w.kt).bytes();
     w.part_floats = (size_t)w.k_slices * (w.slots + kClasses) * (w.ntn * 16) * w.kpad;
     return w;
 }

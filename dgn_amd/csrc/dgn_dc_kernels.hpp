@@ -358,12 +358,13 @@ struct DcWgradParams {
 // KT: k tiles per wave the LDS strips are laid out for; KTW (KT or KT - 1): the k tiles THIS wave accumulates (w + 8 b, b < KTW) -- with
 // k = 420 (27 tiles) three waves own four tiles and five own three: the wave-uniform count is a template argument (MFMAs under run-time
 // guards make the compiler copy the accumulators), every wave runs the same barriers whatever its instantiation.
+__host__ __device__ constexpr wg::StripBufs wgrad_bufs(int ntn, int kt) { return wg::StripBufs{16, ntn * 16 + 4, kt * 128 + 4}; }      // (LDS row strides)
 template <int NTN, int KT, int KTW>
 __device__ __forceinline__ void dc_wgrad_run(const DcWgradParams& p, float* lds_dc) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
     const int k0 = blockIdx.y * p.k_slice, k_here = min(p.k_slice, p.k - k0);
-    constexpr int gs = NTN * 16 + 4, xs = KT * 128 + 4;          // LDS row strides
-    constexpr int half = 16 * (gs + xs);
+    constexpr wg::StripBufs L = wgrad_bufs(NTN, KT);
+    constexpr int gs = L.gs, xs = L.xs, half = L.half();
     const int gq = (p.n + 3) >> 2, xq = (k_here + 3) >> 2, per_row = gq + xq, total = 16 * per_row;
     constexpr int kMaxItems = (16 * (NTN * 4 + KT * 32) + kWave * kWgWaves - 1) / (kWave * kWgWaves);
     // a 16-row strip of G and of X (this k slice), rows gathered through vperm: wg::strip_fetch / strip_commit

@@ -10,11 +10,10 @@ namespace {
 
 template <int NT>
 hipError_t launch_gemm_nt(const GemmParams& p, dim3 grid, hipStream_t st, int wkn) {
-    const size_t lds = (size_t)2 * NT * 16 * kKS * sizeof(float);
     static LdsOptIn lds_ok{0};
     if (hipError_t e = allow_lds(lds_ok, 160 * 1024, &ts_gemm<NT, 0>, &ts_gemm<NT, 1>)) return e;
-    if (wkn) hipLaunchKernelGGL((ts_gemm<NT, 1>), grid, dim3(kWave * kWaves), lds, st, p);
-    else hipLaunchKernelGGL((ts_gemm<NT, 0>), grid, dim3(kWave * kWaves), lds, st, p);
+    if (wkn) hipLaunchKernelGGL((ts_gemm<NT, 1>), grid, dim3(kWave * kWaves), gemm_lds_bytes(NT), st, p);
+    else hipLaunchKernelGGL((ts_gemm<NT, 0>), grid, dim3(kWave * kWaves), gemm_lds_bytes(NT), st, p);
     return hipGetLastError();
 }
 
@@ -57,7 +56,7 @@ WgPlan wgrad_plan(int64_t M, int k, int n) {
     w.k_slices = (k + w.k_slice - 1) / w.k_slice;
     const int64_t n_strips = (M + 15) / 16;
     w.slots = (int)std::max<int64_t>(1, std::min<int64_t>(n_cus(), n_strips));
-    w.lds = (size_t)2 * 16 * ((w.nt * 16 + 4) + (w.kt * 16 + 4)) * sizeof(float);
+    w.lds = wgrad_bufs(w.nt * 16, w.kt * 16).bytes();
     return w;
 }
 
@@ -73,7 +72,7 @@ TwPlan tile_wgrad_plan(int64_t M, int kk, int n) {
     t.kb_tiles = (kt + t.k_blocks - 1) / t.k_blocks;
     const int64_t n_strips = (M + kTwRows - 1) / kTwRows;
     t.slots = (int)std::max<int64_t>(1, std::min<int64_t>(n_strips, n_cus() / (t.n_blocks * t.k_blocks)));
-    t.lds = (size_t)2 * kTwRows * (tw_stride(t.nb_tiles * 32) + tw_stride(t.kb_tiles * 32)) * sizeof(float);
+    t.lds = tw_bufs(t.nb_tiles, t.kb_tiles).bytes();
     return t;
 }
 

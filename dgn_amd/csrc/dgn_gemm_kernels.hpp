@@ -49,10 +49,12 @@ struct GemmParams {
 #else
 #define DGN_GEMM_ATTR
 #endif
+constexpr int gemm_buf_floats(int NT) { return NT * 16 * kKS; }      // ts_gemm's dynamic LDS: two weight-chunk buffers of NT*16 rows
+constexpr size_t gemm_lds_bytes(int NT) { return (size_t)2 * gemm_buf_floats(NT) * sizeof(float); }
 template <int NT, int WKN>
 __global__ __launch_bounds__(kWave * kWaves) DGN_GEMM_ATTR void ts_gemm(const GemmParams p) {
     extern __shared__ float Wc_dyn[];
-    constexpr int kBuf = NT * 16 * kKS;                        // floats per weight-chunk buffer (two of them)
+    constexpr int kBuf = gemm_buf_floats(NT);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
     const int n0 = blockIdx.y * p.n_slice;                    // first output column of this workgroup column
     const int n_here = min(NT * 16, p.n - n0);
@@ -298,14 +300,16 @@ struct WgradParams {
     int slots;
 };
 
+// (LDS row strides == 4 mod 8: spreads the rows over the banks)
+__host__ __device__ constexpr wg::StripBufs wgrad_bufs(int n_cols, int k_cols) { return wg::StripBufs{16, n_cols + 4, k_cols + 4}; }
 template <int KT>
 __global__ __launch_bounds__(kWave * kWgWaves) void ts_gemm_wgrad(const WgradParams p) {
     extern __shared__ float lds_g[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
     const int NTn = (p.n + 15) >> 4;
     const int k0 = blockIdx.y * p.k_slice, k_here = min(KT * 16, p.kk - k0);
-    const int gs = NTn * 16 + 4, xs = KT * 16 + 4;              // LDS row strides (== 4 mod 8... spreads the rows over the banks)
-    const int half = 16 * (gs + xs);                              // floats of one (G strip, X strip) buffer
+    const wg::StripBufs L = wgrad_bufs(NTn * 16, KT * 16);
+    const int gs = L.gs, xs = L.xs, half = L.half();
     auto Gbuf = [&](int b) { return lds_g + b * half; };         // (pointer arithmetic, not a pointer table: a dynamically indexed
     auto Xbuf = [&](int b) { return lds_g + b * half + 16 * gs; };   //  array of pointers would live in scratch memory)
     const int64_t n_strips = (p.M + 15) / 16;
@@ -406,7 +410,8 @@ struct TileWgParams {
     int slots, n_blocks, k_blocks, nb_tiles, kb_tiles;      // tiles of 32 per block (<= 8 each)
 };
 
-__host__ __device__ inline int tw_stride(int cols) { return ((cols + 63) / 64) * 64 + 32; }      // == 32 mod 64: the two half-waves of an operand read hit disjoint banks
+__host__ __device__ constexpr int tw_stride(int cols) { return ((cols + 63) / 64) * 64 + 32; }      // == 32 mod 64: the two half-waves of an operand read hit disjoint banks
+__host__ __device__ constexpr wg::StripBufs tw_bufs(int nb_tiles, int kb_tiles) { return wg::StripBufs{kTwRows, tw_stride(nb_tiles * 32), tw_stride(kb_tiles * 32)}; }
 
 constexpr int kTwItems = (kTwRows * 128 + kWave * kTwWaves - 1) / (kWave * kTwWaves);          // 256 + 256 columns: 4 float4's per thread and strip
 
@@ -485,8 +490,8 @@ __global__ __launch_bounds__(kWave * kTwWaves) void tile_wgrad(const TileWgParam
     TwBlock B;
     B.n0 = bn * p.nb_tiles * 32; B.k0 = bk * p.kb_tiles * 32;
     B.n_here = min(p.nb_tiles * 32, p.n - B.n0); B.k_here = min(p.kb_tiles * 32, p.kk - B.k0);      // columns of this block that exist
-    B.gs = tw_stride(p.nb_tiles * 32); B.xs = tw_stride(p.kb_tiles * 32);
-    B.half = kTwRows * (B.gs + B.xs);
+    const wg::StripBufs L = tw_bufs(p.nb_tiles, p.kb_tiles);
+    B.gs = L.gs; B.xs = L.xs; B.half = L.half();
     B.gq = (B.n_here + 3) >> 2;
     B.per_row = B.gq + ((B.k_here + 3) >> 2);
     B.total = kTwRows * B.per_row;

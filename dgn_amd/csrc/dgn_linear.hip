@@ -11,6 +11,25 @@ hipError_t launch_linear_plain(int nt, int kb, const LinParams& p, int threads, 
 
 namespace {
 bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// one row per ts_linear mode, in the enum's order
+LinLauncher* const kLaunchers[kLinModes] = {launch_linear_plain, launch_linear_combine, launch_linear_expand, launch_linear_bn, launch_linear_act,
+                                            launch_linear_add,   launch_linear_mix,     launch_linear_actm,   launch_linear_bnb};
+
+// the fields every entry point fills: C[t] = A[t] op(W[t]) over M rows, T batch entries (strides and the mode's operands: the caller)
+LinParams lin_params(int64_t M, int k, int n, int T, const float* A, const float* W, int64_t ldw, int w_kn, float* C) {
+    LinParams p{};
+    p.M = M; p.k = k; p.n = n; p.T = T;
+    p.A = A; p.W = W; p.ldw = ldw; p.w_kn = w_kn; p.C = C;
+    return p;
+}
+LinParams combine_params(int64_t M, int k, int T, int S, int fo, const float* a, int64_t stride_a, const float* w, int64_t ldw, int64_t stride_w,
+                         const float* scale, const float* bias, const float* row_scale, float* y, int64_t ld_y) {
+    LinParams p = lin_params(M, k, S * fo, T, a, w, ldw, 0, nullptr);
+    p.sA = stride_a; p.sW = stride_w;
+    p.S = S; p.fo = fo; p.sc = scale; p.rs = row_scale; p.cb = bias; p.Y = y; p.ldy = ld_y;
+    return p;
+}
 }  // namespace
 }  // namespace lin
 }  // namespace dgn
@@ -18,27 +37,19 @@ bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0;
 using namespace dgn;
 using namespace dgn::lin;
 
-
-
 extern "C" int dgn_linear_supported(int32_t k, int32_t n, int32_t wgrad) {
     const bool ok = k >= 2 && n >= 2 && k % 2 == 0 && n % 2 == 0 && k <= 16 * kMaxTiles && n <= 16 * kMaxTiles;
     return ok && (!wgrad || ((n + 15) / 16) * ((k + 15) / 16) <= kMaxWgradTiles);
 }
 
-static int launch_linear(const char* fn, LinParams& p, void* stream) {
+// `mode`: the ts_linear variant the caller filled p for -- threads, tables, WREG eligibility and the launcher all follow from it
+static int launch_linear(const char* fn, int mode, LinParams& p, void* stream) {
     p.kp = lds_stride(p.k);
     const int NT = (p.n + 15) / 16, KB = (p.k + 15) / 16;
-    const bool bn = p.bn_mean != nullptr && p.bnb_gz == nullptr, actm = p.act_z != nullptr, addm = p.add1 != nullptr;
-    const bool mixm = p.out2 != nullptr, maskm = p.act_mask != nullptr, bnbm = p.bnb_gz != nullptr;
-    const int mode = bnbm ? kActMaskBnb : (mixm ? kMixFwd : (bn ? kBnPlain : (actm ? kActPlain : (maskm ? kActMask : (addm ? kAddPlain : kPlain)))));
-    const size_t w_bytes = ((size_t)NT * 16 * p.kp + 2 * NT * 16 + (bnbm ? 5 * NT * 16 : (bn ? 4 * KB * 16 : (actm ? KB * 16 : 0)))) * 4;
-    // (LinParams.bn_part: 4 fp64 cells per lane and epilogue trip, per wave, behind everything else)
-    const size_t stat_bytes = p.bn_part ? (size_t)4 * ((kStrip * (p.fo >> 1) + 63) / 64) * 64 * sizeof(double) : 0;
-    const size_t strip_bytes = ((size_t)strip_floats(p.k) + kStrip * p.n + kFacFloats) * 4 + stat_bytes;
-    int waves = linear_threads(NT, KB, mode) / 64;
-    p.wreg = (p.ex.gy || p.S > 0) && !bnbm && linear_wreg_ok(NT, KB, p.ex.gy ? kExpand : kCombine) && (option(OPT_LIN_WREG) & (p.ex.gy ? 2 : 1)) ? 1 : 0;      // (bit 0: combine epilogue, bit 1: expanded operand)
-    if (p.wreg) waves = std::min(waves, 4);
-    while (waves > 1 && w_bytes + waves * strip_bytes > (size_t)kLdsBudget) waves = waves == 12 ? 8 : waves / 2;
+    p.wreg = linear_wreg_ok(NT, KB, mode) && (option(OPT_LIN_WREG) & (mode == kExpand ? 2 : 1)) ? 1 : 0;      // (bit 0: combine epilogue, bit 1: expanded operand)
+    auto lds_bytes = [&](int waves, bool wreg) { return linear_lds_bytes(NT, KB, mode, wreg, p.k, p.n, p.kp, waves, p.bn_part ? p.fo : 0, &p.st_off); };
+    int waves = linear_threads(NT, KB, mode, p.wreg) / 64;
+    while (waves > 1 && lds_bytes(waves, false) > (size_t)kLdsBudget) waves = waves == 12 ? 8 : waves / 2;      // (sized without WREG's overlay)
     const int64_t n_strips = (p.M + kStrip - 1) / kStrip;
     {   // Small batches: 2 970 rows are 186 strips -- twelve 16-wave workgroups on twelve of 256 CUs.  Fewer waves per workgroup until
         // the strips cover the chip (every workgroup stages the weights itself: 20 KB from L2).
@@ -46,28 +57,11 @@ static int launch_linear(const char* fn, LinParams& p, void* stream) {
         const int min_waves = (int)option(OPT_LINEAR_SMALL_MIN_WAVES);           // (4: no gain, 2 and 1: slower -- the weights are staged by too few threads)
         while (!keep && waves > min_waves && n_strips * p.T < (int64_t)n_cus() * waves) waves = waves == 12 ? 8 : waves / 2;
     }
-    const size_t wl_bytes = (size_t)NT * 16 * p.kp * 4;
-    size_t lds = p.wreg ? w_bytes - wl_bytes + std::max(wl_bytes, waves * (strip_bytes - stat_bytes)) : w_bytes + waves * (strip_bytes - stat_bytes);
-    if (p.bn_part) {
-        lds = (lds + 7) & ~(size_t)7;
-        p.st_off = (int)(lds / 4);
-        lds += waves * stat_bytes;
-    }
+    const size_t lds = lds_bytes(waves, p.wreg);
     if (lds > (size_t)kLdsBudget) { set_error("%s: weights do not fit in LDS", fn); return -1; }
     const int per_cu = std::max(1, std::min({(int)(kLdsBudget / lds), 32 / waves, p.wreg ? 3 : 32}));      // (WREG: 3 waves per SIMD by registers)
-    int groups = std::max(1, n_cus() * per_cu / p.T);
-    groups = (int)std::min<int64_t>(groups, (n_strips + waves - 1) / waves);
-    p.groups = groups;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const hipError_t e = p.ex.gy ? launch_linear_expand(NT, KB, p, waves * 64, lds, st)
-                       : bnbm    ? launch_linear_bnb(NT, KB, p, waves * 64, lds, st)
-                       : p.S > 0 ? launch_linear_combine(NT, KB, p, waves * 64, lds, st)
-                       : mixm    ? launch_linear_mix(NT, KB, p, waves * 64, lds, st)
-                       : bn      ? launch_linear_bn(NT, KB, p, waves * 64, lds, st)
-                       : actm    ? launch_linear_act(NT, KB, p, waves * 64, lds, st)
-                       : maskm   ? launch_linear_actm(NT, KB, p, waves * 64, lds, st)
-                       : addm    ? launch_linear_add(NT, KB, p, waves * 64, lds, st)
-                                 : launch_linear_plain(NT, KB, p, waves * 64, lds, st);
+    p.groups = (int)std::min<int64_t>(std::max(1, n_cus() * per_cu / p.T), (n_strips + waves - 1) / waves);
+    const hipError_t e = kLaunchers[mode](NT, KB, p, waves * 64, lds, static_cast<hipStream_t>(stream));
     DGN_HIP_CHECK(e);
     return 0;
 }
@@ -84,13 +78,10 @@ extern "C" int dgn_linear_forward(int64_t n_rows, int32_t k, int32_t n, int32_t 
         set_error("%s: A and C must have dense rows (lda == k, ldc == n) and 8-byte aligned batch entries", fn);
         return -1;
     }
-    LinParams p{};
-    p.M = n_rows; p.k = k; p.n = n; p.T = batch;
-    p.A = a; p.sA = stride_a;
-    p.W = w; p.ldw = ldw; p.sW = stride_w; p.w_kn = w_is_kn;
+    LinParams p = lin_params(n_rows, k, n, batch, a, w, ldw, w_is_kn, c);
+    p.sA = stride_a; p.sW = stride_w; p.sC = stride_c;
     p.bias = bias; p.sBias = stride_bias;
-    p.C = c; p.sC = stride_c;
-    return launch_linear(fn, p, stream);
+    return launch_linear(fn, kPlain, p, stream);
 }
 
 extern "C" int dgn_linear_forward_bn(int64_t n_rows, int32_t k, int32_t n, const float* a, const float* w, int64_t ldw, int32_t w_is_kn,
@@ -101,17 +92,14 @@ extern "C" int dgn_linear_forward_bn(int64_t n_rows, int32_t k, int32_t n, const
     if (n_rows == 0) return 0;
     if (!a || !w || !c || !bn_mean || !bn_invstd) { set_error("%s: null operand", fn); return -1; }
     if (!aligned8(a) || !aligned8(c)) { set_error("%s: A and C must be 8-byte aligned (dense rows)", fn); return -1; }
-    LinParams p{};
-    p.M = n_rows; p.k = k; p.n = n; p.T = 1;
-    p.A = a; p.W = w; p.ldw = ldw; p.w_kn = w_is_kn;
+    LinParams p = lin_params(n_rows, k, n, 1, a, w, ldw, w_is_kn, c);
     p.bias = bias;
-    p.C = c;
     p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.bn_gamma = bn_gamma; p.bn_beta = bn_beta;
-    return launch_linear(fn, p, stream);
+    return launch_linear(fn, kBnPlain, p, stream);
 }
 
 extern "C" int dgn_linear_add_supported(int32_t k, int32_t n) {
-    return dgn_linear_supported(k, n, 0) && linear_add_shape_ok((n + 15) / 16, (k + 15) / 16);
+    return dgn_linear_supported(k, n, 0) && linear_shape_ok((n + 15) / 16, (k + 15) / 16, kAddPlain);
 }
 
 extern "C" int dgn_linear_forward_add(int64_t n_rows, int32_t k, int32_t n, const float* a, const float* w, int64_t ldw, int32_t w_is_kn,
@@ -121,12 +109,9 @@ extern "C" int dgn_linear_forward_add(int64_t n_rows, int32_t k, int32_t n, cons
     if (n_rows == 0) return 0;
     if (!a || !w || !c || !add1) { set_error("%s: null operand", fn); return -1; }
     if (!aligned8(a) || !al16(c) || !al16(add1) || (add2 && !al16(add2))) { set_error("%s: a must be 8-byte, c / add1 / add2 16-byte aligned (dense rows)", fn); return -1; }
-    LinParams p{};
-    p.M = n_rows; p.k = k; p.n = n; p.T = 1;
-    p.A = a; p.W = w; p.ldw = ldw; p.w_kn = w_is_kn;
-    p.C = c;
+    LinParams p = lin_params(n_rows, k, n, 1, a, w, ldw, w_is_kn, c);
     p.add1 = add1; p.add2 = add2;
-    return launch_linear(fn, p, stream);
+    return launch_linear(fn, kAddPlain, p, stream);
 }
 
 extern "C" int dgn_linear_forward_bn_act(int64_t n_rows, int32_t k, int32_t n, const float* a, const float* w, int64_t ldw, const float* bn_mean,
@@ -137,17 +122,14 @@ extern "C" int dgn_linear_forward_bn_act(int64_t n_rows, int32_t k, int32_t n, c
     if (n_rows == 0) return 0;
     if (!a || !w || !z_out || !out || !bn_mean || !bn_invstd) { set_error("%s: null operand", fn); return -1; }
     if (!aligned8(a) || !al16(z_out) || !al16(out) || (residual && !al16(residual))) { set_error("%s: a must be 8-byte, z_out / out / residual 16-byte aligned", fn); return -1; }
-    LinParams p{};
-    p.M = n_rows; p.k = k; p.n = n; p.T = 1;
-    p.A = a; p.W = w; p.ldw = ldw; p.w_kn = 0;
-    p.C = z_out;
+    LinParams p = lin_params(n_rows, k, n, 1, a, w, ldw, 0, z_out);
     p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.bn_gamma = bn_gamma; p.bn_beta = bn_beta;
     p.ep_bias = act_bias; p.act_kind = act; p.act_slope = slope; p.add1 = residual; p.out2 = out;
-    return launch_linear(fn, p, stream);
+    return launch_linear(fn, kMixFwd, p, stream);
 }
 
 extern "C" int dgn_linear_act_supported(int32_t k, int32_t n) {
-    return dgn_linear_supported(k, n, 0) && linear_act_shape_ok((n + 15) / 16, (k + 15) / 16);
+    return dgn_linear_supported(k, n, 0) && linear_shape_ok((n + 15) / 16, (k + 15) / 16, kActPlain);
 }
 
 extern "C" int dgn_linear_forward_act(int64_t n_rows, int32_t k, int32_t n, const float* g, const float* z, const float* act_bias, int32_t act,
@@ -157,12 +139,9 @@ extern "C" int dgn_linear_forward_act(int64_t n_rows, int32_t k, int32_t n, cons
     if (n_rows == 0) return 0;
     if (!g || !z || !w || !c) { set_error("%s: null operand", fn); return -1; }
     if (!aligned8(g) || !aligned8(z) || !aligned8(c) || (gz_out && !al16(gz_out))) { set_error("%s: operands must be 8-byte aligned (dense rows), gz_out 16-byte aligned", fn); return -1; }
-    LinParams p{};
-    p.M = n_rows; p.k = k; p.n = n; p.T = 1;
-    p.A = g; p.W = w; p.ldw = ldw; p.w_kn = w_is_kn;
-    p.C = c;
+    LinParams p = lin_params(n_rows, k, n, 1, g, w, ldw, w_is_kn, c);
     p.act_z = z; p.act_bias = act_bias; p.act_kind = act; p.act_slope = slope; p.gz_out = gz_out;
-    return launch_linear(fn, p, stream);
+    return launch_linear(fn, kActPlain, p, stream);
 }
 
 extern "C" size_t dgn_linear_act_mask_bytes(int64_t n_rows, int32_t n) { return n_rows > 0 && n > 0 ? (((size_t)n_rows * n / 2) + 15) & ~(size_t)15 : 0; }
@@ -175,13 +154,11 @@ extern "C" int dgn_linear_forward_bn_act_mask(int64_t n_rows, int32_t k, int32_t
     if (n_rows == 0) return 0;
     if (!a || !w || !zmask_out || !out || !bn_mean || !bn_invstd) { set_error("%s: null operand", fn); return -1; }
     if (!aligned8(a) || !al16(zmask_out) || !al16(out) || (residual && !al16(residual))) { set_error("%s: a must be 8-byte, zmask_out / out / residual 16-byte aligned", fn); return -1; }
-    LinParams p{};
-    p.M = n_rows; p.k = k; p.n = n; p.T = 1;
-    p.A = a; p.W = w; p.ldw = ldw; p.w_kn = 0;
-    p.C = nullptr; p.zmask_out = zmask_out;
+    LinParams p = lin_params(n_rows, k, n, 1, a, w, ldw, 0, nullptr);
+    p.zmask_out = zmask_out;
     p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.bn_gamma = bn_gamma; p.bn_beta = bn_beta;
     p.ep_bias = act_bias; p.act_kind = act; p.act_slope = slope; p.add1 = residual; p.out2 = out;
-    return launch_linear(fn, p, stream);
+    return launch_linear(fn, kMixFwd, p, stream);
 }
 
 extern "C" int dgn_linear_forward_act_mask(int64_t n_rows, int32_t k, int32_t n, const float* g, const unsigned char* zmask, int32_t act, float slope,
@@ -191,16 +168,13 @@ extern "C" int dgn_linear_forward_act_mask(int64_t n_rows, int32_t k, int32_t n,
     if (n_rows == 0) return 0;
     if (!g || !zmask || !w || !c) { set_error("%s: null operand", fn); return -1; }
     if (!aligned8(g) || (reinterpret_cast<uintptr_t>(zmask) & 1) || !aligned8(c) || (gz_out && !al16(gz_out))) { set_error("%s: g / c must be 8-byte aligned (dense rows), zmask 2-byte, gz_out 16-byte aligned", fn); return -1; }
-    LinParams p{};
-    p.M = n_rows; p.k = k; p.n = n; p.T = 1;
-    p.A = g; p.W = w; p.ldw = ldw; p.w_kn = w_is_kn;
-    p.C = c;
+    LinParams p = lin_params(n_rows, k, n, 1, g, w, ldw, w_is_kn, c);
     p.act_mask = zmask; p.act_kind = act; p.act_slope = slope; p.gz_out = gz_out;
-    return launch_linear(fn, p, stream);
+    return launch_linear(fn, kActMask, p, stream);
 }
 
 extern "C" int dgn_linear_bnb_supported(int32_t k, int32_t n) {
-    return dgn_linear_act_supported(k, n) && dgn_linear_add_supported(k, n) && linear_bnb_shape_ok((n + 15) / 16, (k + 15) / 16);
+    return dgn_linear_supported(k, n, 0) && linear_shape_ok((n + 15) / 16, (k + 15) / 16, kActMaskBnb);
 }
 
 extern "C" int dgn_linear_forward_act_mask_bnb(int64_t n_rows, int32_t k, int32_t n, const float* g, const unsigned char* zmask, int32_t act, float slope,
@@ -218,13 +192,11 @@ extern "C" int dgn_linear_forward_act_mask_bnb(int64_t n_rows, int32_t k, int32_
         set_error("%s: g 8-byte, zmask 2-byte, y 16-byte, gz 8-byte aligned (dense rows, even tower stride)", fn);
         return -1;
     }
-    LinParams p{};
-    p.M = n_rows; p.k = k; p.n = n; p.T = 1;
-    p.A = g; p.W = w; p.ldw = ldw; p.w_kn = w_is_kn;
+    LinParams p = lin_params(n_rows, k, n, 1, g, w, ldw, w_is_kn, nullptr);
     p.act_mask = zmask; p.act_kind = act; p.act_slope = slope;
     p.bnb_y = y; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.bn_gamma = bn_gamma; p.bnb_sums = sums; p.rs = row_scale; p.fo = f_out;
     p.bnb_gz = gz; p.bnb_sT = stride_gz;
-    return launch_linear(fn, p, stream);
+    return launch_linear(fn, kActMaskBnb, p, stream);
 }
 
 extern "C" int dgn_linear_combine_forward(int64_t n_rows, int32_t k, int32_t n_towers, int32_t n_scalers, int32_t f_out,
@@ -241,12 +213,8 @@ extern "C" int dgn_linear_combine_forward(int64_t n_rows, int32_t k, int32_t n_t
     if (!a || !w || !y || (n_scalers > 1 && !scale)) { set_error("%s: null operand", fn); return -1; }
     if ((f_out & 1) || (ld_y & 1) || !aligned8(y)) { set_error("%s: f_out and ld_y must be even, y 8-byte aligned", fn); return -1; }
     if ((stride_a & 1) || !aligned8(a) || ld_y < (int64_t)n_towers * f_out) { set_error("%s: A entries must be 8-byte aligned, y rows n_towers * f_out wide", fn); return -1; }
-    LinParams p{};
-    p.M = n_rows; p.k = k; p.n = n; p.T = n_towers;
-    p.A = a; p.sA = stride_a;
-    p.W = w; p.ldw = ldw; p.sW = stride_w; p.w_kn = 0;
-    p.S = n_scalers; p.fo = f_out; p.sc = scale; p.rs = row_scale; p.cb = bias; p.Y = y; p.ldy = ld_y;
-    return launch_linear(fn, p, stream);
+    LinParams p = combine_params(n_rows, k, n_towers, n_scalers, f_out, a, stride_a, w, ldw, stride_w, scale, bias, row_scale, y, ld_y);
+    return launch_linear(fn, kCombine, p, stream);
 }
 
 size_t dgn::lin::combine_forward_stats_bytes(int32_t n_towers, int32_t f_out) {
@@ -262,13 +230,9 @@ int dgn::lin::combine_forward_stats(int64_t n_rows, int32_t k, int32_t n_towers,
         !a || !w || !y || (n_scalers > 1 && !scale) || (ld_y & 1) || !aligned8(y) || (stride_a & 1) || !aligned8(a) || ld_y != (int64_t)n_towers * f_out || !part ||
         part_bytes < combine_forward_stats_bytes(n_towers, f_out))
         return 1;
-    LinParams p{};
-    p.M = n_rows; p.k = k; p.n = n; p.T = n_towers;
-    p.A = a; p.sA = stride_a;
-    p.W = w; p.ldw = ldw; p.sW = stride_w; p.w_kn = 0;
-    p.S = n_scalers; p.fo = f_out; p.sc = scale; p.rs = row_scale; p.cb = bias; p.Y = y; p.ldy = ld_y;
+    LinParams p = combine_params(n_rows, k, n_towers, n_scalers, f_out, a, stride_a, w, ldw, stride_w, scale, bias, row_scale, y, ld_y);
     p.bn_part = part; p.bn_F = n_towers * f_out;
-    const int rc = launch_linear(fn, p, stream);
+    const int rc = launch_linear(fn, kCombine, p, stream);
     if (rc == 0) *groups = p.groups;
     return rc;
 }
@@ -296,11 +260,8 @@ static int launch_wgrad(const char* fn, WgParams& p, float* dw, int64_t lddw, in
     p.groups = wgrad_groups(p.M, k, n, batch);
     p.ones = dbias != nullptr;
     const int NT = (n + 15) / 16, KT = (k + 15) / 16;
-    size_t lds = std::max((size_t)4 * wgrad_wave_floats(n, k, p.g_mask != nullptr), (size_t)NT * 16 * KT * 16) * 4;
-    if (p.bn_mean) {
-        p.bn_off = (int)(lds / 4);
-        lds += (size_t)4 * KT * 16 * 4;
-    }
+    if (p.bn_mean) p.bn_off = wgrad_bn_off(NT, KT, n, k, p.g_mask != nullptr);
+    const size_t lds = wgrad_lds_bytes(NT, KT, n, k, p.g_mask != nullptr, p.bn_mean != nullptr);
     const hipError_t e = p.ex.gy ? launch_wgrad_expand(NT, KT, p, lds, st) : (p.g_mask ? launch_wgrad_gmask(NT, KT, p, lds, st) : launch_wgrad_plain(NT, KT, p, lds, st));
     DGN_HIP_CHECK(e);
     const int64_t total = (int64_t)batch * n * (dbias ? k + 1 : k);
@@ -319,24 +280,33 @@ static int zero_wgrad(float* dw, int64_t lddw, int64_t stride_dw, float* dbias, 
     return 0;
 }
 
+// The weight-gradient entry points' opening: the shape tests, and the empty batch's zero fill.  1: go on, else the return value
+static int wgrad_open(const char* fn, int64_t n_rows, int k, int n, int batch, float* dw, int64_t lddw, int64_t stride_dw, float* dbias,
+                      int64_t stride_dbias, void* stream) {
+    if (dbias && k % 16 == 0) { set_error("%s: the bias gradient rides in X's padding column (k %% 16 != 0)", fn); return -1; }
+    if (n_rows < 0 || batch < 1 || !dgn_linear_supported(k, n, 1)) { set_error("%s: need even k, n in [2, 160] and at most 45 tiles (k=%d n=%d)", fn, k, n); return -1; }
+    if (!dw) { set_error("%s: null output", fn); return -1; }
+    return n_rows == 0 ? zero_wgrad(dw, lddw, stride_dw, dbias, stride_dbias, k, n, batch, static_cast<hipStream_t>(stream)) : 1;
+}
+static WgParams wg_params(int64_t M, int k, int n, int T, const float* G, const float* X) {
+    WgParams p{};
+    p.M = M; p.n = n; p.k = k; p.T = T; p.G = G; p.X = X;
+    return p;
+}
+
 extern "C" int dgn_linear_wgrad(int64_t n_rows, int32_t k, int32_t n, int32_t batch, const float* g, int64_t ldg,
                                 int64_t stride_g, const float* x, int64_t ldx, int64_t stride_x, float* dw, int64_t lddw,
                                 int64_t stride_dw, float* dbias, int64_t stride_dbias, void* ws, size_t ws_bytes,
                                 void* stream) {
     const char* fn = "dgn_linear_wgrad";
-    if (dbias && k % 16 == 0) { set_error("%s: the bias gradient rides in X's padding column (k %% 16 != 0)", fn); return -1; }
-    if (n_rows < 0 || batch < 1 || !dgn_linear_supported(k, n, 1)) { set_error("%s: need even k, n in [2, 160] and at most 45 tiles (k=%d n=%d)", fn, k, n); return -1; }
-    if (!dw) { set_error("%s: null output", fn); return -1; }
-    if (n_rows == 0) return zero_wgrad(dw, lddw, stride_dw, dbias, stride_dbias, k, n, batch, static_cast<hipStream_t>(stream));
+    if (const int rc = wgrad_open(fn, n_rows, k, n, batch, dw, lddw, stride_dw, dbias, stride_dbias, stream); rc != 1) return rc;
     if (!g || !x) { set_error("%s: null operand", fn); return -1; }
     if (ldg != n || ldx != k || (stride_g & 1) || (stride_x & 1) || !aligned8(g) || !aligned8(x)) {
         set_error("%s: G and X must have dense rows (ldg == n, ldx == k) and 8-byte aligned batch entries", fn);
         return -1;
     }
-    WgParams p{};
-    p.M = n_rows; p.n = n; p.k = k; p.T = batch;
-    p.G = g; p.sG = stride_g;
-    p.X = x; p.sX = stride_x;
+    WgParams p = wg_params(n_rows, k, n, batch, g, x);
+    p.sG = stride_g; p.sX = stride_x;
     return launch_wgrad(fn, p, dw, lddw, stride_dw, dbias, stride_dbias, ws, ws_bytes, stream);
 }
 
@@ -344,14 +314,9 @@ extern "C" int dgn_linear_wgrad_bn(int64_t n_rows, int32_t k, int32_t n, const f
                                    const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, void* ws,
                                    size_t ws_bytes, void* stream) {
     const char* fn = "dgn_linear_wgrad_bn";
-    if (dbias && k % 16 == 0) { set_error("%s: the bias gradient rides in X's padding column (k %% 16 != 0)", fn); return -1; }
-    if (n_rows < 0 || !dgn_linear_supported(k, n, 1)) { set_error("%s: need even k, n in [2, 160] and at most 45 tiles (k=%d n=%d)", fn, k, n); return -1; }
-    if (!dw) { set_error("%s: null output", fn); return -1; }
-    if (n_rows == 0) return zero_wgrad(dw, lddw, 0, dbias, 0, k, n, 1, static_cast<hipStream_t>(stream));
+    if (const int rc = wgrad_open(fn, n_rows, k, n, 1, dw, lddw, 0, dbias, 0, stream); rc != 1) return rc;
     if (!g || !x || !bn_mean || !bn_invstd || !aligned8(g) || !aligned8(x)) { set_error("%s: null or misaligned operand", fn); return -1; }
-    WgParams p{};
-    p.M = n_rows; p.n = n; p.k = k; p.T = 1;
-    p.G = g; p.X = x;
+    WgParams p = wg_params(n_rows, k, n, 1, g, x);
     p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.bn_gamma = bn_gamma; p.bn_beta = bn_beta;
     return launch_wgrad(fn, p, dw, lddw, 0, dbias, 0, ws, ws_bytes, stream);
 }
@@ -360,17 +325,12 @@ extern "C" int dgn_linear_wgrad_bn_act_mask(int64_t n_rows, int32_t k, int32_t n
                                             const float* x, float* dw, int64_t lddw, float* dbias, const float* bn_mean, const float* bn_invstd,
                                             const float* bn_gamma, const float* bn_beta, void* ws, size_t ws_bytes, void* stream) {
     const char* fn = "dgn_linear_wgrad_bn_act_mask";
-    if (dbias && k % 16 == 0) { set_error("%s: the bias gradient rides in X's padding column (k %% 16 != 0)", fn); return -1; }
-    if (n_rows < 0 || !dgn_linear_supported(k, n, 1)) { set_error("%s: need even k, n in [2, 160] and at most 45 tiles (k=%d n=%d)", fn, k, n); return -1; }
-    if (!dw) { set_error("%s: null output", fn); return -1; }
-    if (n_rows == 0) return zero_wgrad(dw, lddw, 0, dbias, 0, k, n, 1, static_cast<hipStream_t>(stream));
+    if (const int rc = wgrad_open(fn, n_rows, k, n, 1, dw, lddw, 0, dbias, 0, stream); rc != 1) return rc;
     if (!g || !zmask || !x || !bn_mean || !bn_invstd || !aligned8(g) || !aligned8(x) || !al16(zmask)) {
         set_error("%s: null or misaligned operand (g, x 8-byte; zmask 16-byte: its strips travel as 16-byte direct-to-LDS pieces)", fn);
         return -1;
     }
-    WgParams p{};
-    p.M = n_rows; p.n = n; p.k = k; p.T = 1;
-    p.G = g; p.X = x;
+    WgParams p = wg_params(n_rows, k, n, 1, g, x);
     p.g_mask = zmask; p.act_kind = act; p.act_slope = slope;
     p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.bn_gamma = bn_gamma; p.bn_beta = bn_beta;
     return launch_wgrad(fn, p, dw, lddw, 0, dbias, 0, ws, ws_bytes, stream);
@@ -398,13 +358,11 @@ extern "C" int dgn_linear_combine_backward_input(int64_t n_rows, int32_t n_tower
     if (!dgn_linear_supported(red, k, 0)) { set_error("%s: need even widths in [2, 160] (S*f_out=%d k=%d)", fn, red, k); return -1; }
     if (n_rows == 0) return 0;
     if (!w || !g_a || (stride_ga & 1) || !aligned8(g_a)) { set_error("%s: null or misaligned operand", fn); return -1; }
-    LinParams p{};
-    p.M = n_rows; p.k = red; p.n = k; p.T = n_towers;
-    p.W = w; p.ldw = ldw; p.sW = stride_w; p.w_kn = 1;
-    p.C = g_a; p.sC = stride_ga;
+    LinParams p = lin_params(n_rows, red, k, n_towers, nullptr, w, ldw, 1, g_a);
+    p.sW = stride_w; p.sC = stride_ga;
     if (n_scalers == 1) { p.A = gy; p.sA = stride_gy; }      // nothing to expand: gy is the operand
-    else { p.ex.gy = gy; p.ex.sT = stride_gy; p.ex.sc = scale; p.ex.S = n_scalers; p.ex.fo = f_out; }
-    return launch_linear(fn, p, stream);
+    else p.ex = ExpandSrc{gy, stride_gy, scale, n_scalers, f_out};
+    return launch_linear(fn, n_scalers == 1 ? kPlain : kExpand, p, stream);
 }
 
 extern "C" int dgn_linear_combine_backward_weight(int64_t n_rows, int32_t n_towers, int32_t n_scalers, int32_t f_out, int32_t k,
@@ -440,11 +398,10 @@ int dgn::lin::combine_backward_weight_bias_pick(int64_t n_rows, int32_t n_towers
         return zero_wgrad(dw, lddw, stride_dw, g_sum, n, k, n, n_towers, static_cast<hipStream_t>(stream));
     }
     if (!a || (stride_a & 1) || !aligned8(a)) { set_error("%s: null or misaligned operand", fn); return -1; }
-    WgParams p{};
-    p.M = n_rows; p.n = n; p.k = k; p.T = n_towers;
-    p.X = a; p.sX = stride_a;
+    WgParams p = wg_params(n_rows, k, n, n_towers, nullptr, a);
+    p.sX = stride_a;
     if (n_scalers == 1) { p.G = gy; p.sG = stride_gy; }
-    else { p.ex.gy = gy; p.ex.sT = stride_gy; p.ex.sc = scale; p.ex.S = n_scalers; p.ex.fo = f_out; }
+    else p.ex = ExpandSrc{gy, stride_gy, scale, n_scalers, f_out};
     if (pick && (!g_sum || pick_slot < 0 || pick_slot >= n_scalers)) { set_error("%s: pick needs g_sum and a scaler slot", fn); return -1; }
     return launch_wgrad(fn, p, dw, lddw, stride_dw, g_sum, n, ws, ws_bytes, stream, pick, pick_slot * f_out, f_out);
 }

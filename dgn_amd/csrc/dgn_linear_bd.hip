@@ -39,6 +39,19 @@ constexpr int bd_fwd_threads(int T, int FB) { return T * FB <= 3 ? 1024 : (T * F
 constexpr int bd_bwd_threads(int T, int FB) { return T * FB <= 2 ? 1024 : (T * FB <= 5 ? 512 : 256); }
 constexpr int bd_wg_waves_per_simd(int T, int FB) { return 2 * T * FB * FB <= 10 ? 2 : 1; }
 
+// The kernels' dynamic LDS, in floats: [weight tiles][bias tiles][a strip block per wave]; the weight-gradient kernels fold their
+// accumulator block [2 T FB^2][16][16] over all of it at the end.  The kernels take their pointers from here, the host its byte counts.
+enum { kBdFwd = 0, kBdBwd = 1, kBdWg = 2, kBdBoth = 3 };
+struct BdLayout { int bias, strips, wave, fold; };
+constexpr BdLayout bd_layout(int which, int T, int fi) {
+    const int FB = (fi + 15) / 16, k = T * fi, w_fwd = T * 2 * FB * 16 * (16 * FB + 4), w_bwd = T * FB * 16 * (32 * FB + 4), fold = 2 * T * FB * FB * 256;
+    return which == kBdFwd   ? BdLayout{w_fwd, w_fwd + T * 2 * FB * 16, kStrip * 2 * k, 0}      // (the results, 16 x 2k, take the operand strip's place)
+           : which == kBdBwd ? BdLayout{w_bwd, w_bwd, strip_floats(2 * k), 0}
+           : which == kBdWg  ? BdLayout{0, 0, strip_floats(2 * k) + strip_floats(k), fold}
+                             : BdLayout{w_bwd, w_bwd, strip_floats(2 * k) + strip_floats(k), fold};
+}
+constexpr size_t bd_lds_bytes(const BdLayout& L, int waves) { return (size_t)std::max(L.strips + waves * L.wave, L.fold) * 4; }
+
 __device__ __forceinline__ f4 bd_operand(const float* x, int valid) {      // four consecutive floats from an 8-byte aligned address,
     const float2 lo = *reinterpret_cast<const float2*>(x), hi = *reinterpret_cast<const float2*>(x + 2);      // entries >= valid zeroed
     return f4{valid > 0 ? lo.x : 0.f, valid > 1 ? lo.y : 0.f, valid > 2 ? hi.x : 0.f, valid > 3 ? hi.y : 0.f};
@@ -84,14 +97,15 @@ __global__ __launch_bounds__(bd_fwd_threads(T, (FI + 15) / 16)) void bd_forward(
     constexpr int KPB = 16 * FB + 4, NTL = T * 2 * FB, NL = 2 * T * FB, NLC = 4 * T * FB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
     constexpr int k = T * fi, n = 2 * k;
+    constexpr BdLayout L = bd_layout(kBdFwd, T, FI);
     float* Wl = lds;                                 // [T][2][FB][16][KPB]: tile (t, j, q) row = output column 16 q + row of the tower
-    float* Bl = Wl + NTL * 16 * KPB;                 // [T][2][FB][16]
-    float* U = Bl + NTL * 16 + wave * (kStrip * n);  // this wave's strip (16 k floats), later its results (16 n floats)
+    float* Bl = lds + L.bias;                        // [T][2][FB][16]
+    float* U = lds + L.strips + wave * L.wave;       // this wave's strip (16 k floats), later its results (16 n floats)
     const int64_t n_strips = (p.M + kStrip - 1) / kStrip;
     const int64_t first = (int64_t)blockIdx.x * n_waves + wave, step = (int64_t)p.groups * n_waves;
     float2 pre[NL];
     if (first < n_strips) load_strip<NL>(pre, p.A, p.M, k, first, lane);
-    for (int i = tid; i < NTL * 16 * KPB + NTL * 16; i += blockDim.x) lds[i] = 0.f;
+    for (int i = tid; i < L.strips; i += blockDim.x) lds[i] = 0.f;
     __syncthreads();
     for (int i = tid; i < 2 * T * fi * fi; i += blockDim.x) {
         const int b = i % fi, a = (i / fi) % fi, tj = i / (fi * fi), t = tj >> 1, j = tj & 1;
@@ -169,13 +183,14 @@ __global__ __launch_bounds__(bd_bwd_threads(T, (FI + 15) / 16)) void bd_backward
     constexpr int KP2 = 32 * FB + 4, NTL = T * FB, NL = 4 * T * FB, NLC = 2 * T * FB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
     constexpr int n = T * fi, k2 = 2 * n;
+    constexpr BdLayout L = bd_layout(kBdBwd, T, FI);
     float* Wl = lds;                                 // [T][FB][16][KP2]: tile (t, q) row = output column c, k index = j 16 FB + r
-    float* U = Wl + NTL * 16 * KP2 + wave * strip_floats(k2);
+    float* U = lds + L.strips + wave * L.wave;
     const int64_t n_strips = (p.M + kStrip - 1) / kStrip;
     const int64_t first = (int64_t)blockIdx.x * n_waves + wave, step = (int64_t)p.groups * n_waves;
     float2 pre[NL];
     if (first < n_strips) load_strip<NL>(pre, p.A, p.M, k2, first, lane);
-    for (int i = tid; i < NTL * 16 * KP2; i += blockDim.x) lds[i] = 0.f;
+    for (int i = tid; i < L.strips; i += blockDim.x) lds[i] = 0.f;
     __syncthreads();
     for (int i = tid; i < 2 * T * fi * fi; i += blockDim.x) {
         const int c = i % fi, r = (i / fi) % fi, tj = i / (fi * fi), t = tj >> 1, j = tj & 1;
@@ -258,9 +273,10 @@ __global__ __launch_bounds__(256, bd_wg_waves_per_simd(T, (FI + 15) / 16)) void 
     constexpr int NLG = 4 * T * FB, NLX = 2 * T * FB, NTL = 2 * T * FB * FB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
     constexpr int k = T * fi, n2 = 2 * k;
-    float* Gl = lds + wave * (strip_floats(n2) + strip_floats(k));
+    constexpr BdLayout L = bd_layout(kBdWg, T, FI);
+    float* Gl = lds + L.strips + wave * L.wave;
     float* Xl = Gl + strip_floats(n2);
-    for (int i = lane; i < strip_floats(n2) + strip_floats(k); i += 64) Gl[i] = 0.f;
+    for (int i = lane; i < L.wave; i += 64) Gl[i] = 0.f;
     const int64_t n_strips = (p.M + kStrip - 1) / kStrip;
     const int64_t first = (int64_t)blockIdx.x * n_waves + wave, step = (int64_t)p.groups * n_waves;
     float2 pg[NLG], px[NLX];
@@ -326,8 +342,9 @@ __global__ __launch_bounds__(512) void bd_backward_both(BdParams p) {
     constexpr int KP2 = 32 * FB + 4, NTL = T * FB, NLG = 4 * T * FB, NLX = 2 * T * FB, NLC = 2 * T * FB, NTW = 2 * T * FB * FB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
     constexpr int n = T * fi, k2 = 2 * n;
+    constexpr BdLayout L = bd_layout(kBdBoth, T, FI);
     float* Wl = lds;                                 // [T][FB][16][KP2] as in bd_backward_input
-    float* U = Wl + NTL * 16 * KP2 + wave * (strip_floats(k2) + strip_floats(n));      // this wave's g strip, later its input-gradient rows
+    float* U = lds + L.strips + wave * L.wave;       // this wave's g strip, later its input-gradient rows
     float* Xl = U + strip_floats(k2);                // this wave's h strip
     const int64_t n_strips = (p.M + kStrip - 1) / kStrip;
     const int64_t first = (int64_t)blockIdx.x * n_waves + wave, step = (int64_t)p.groups * n_waves;
@@ -336,8 +353,8 @@ __global__ __launch_bounds__(512) void bd_backward_both(BdParams p) {
         load_strip<NLG>(pg, p.A, p.M, k2, first, lane);
         load_strip<NLX>(px, p.X, p.M, n, first, lane);
     }
-    for (int i = tid; i < NTL * 16 * KP2; i += blockDim.x) lds[i] = 0.f;
-    for (int i = lane; i < strip_floats(k2) + strip_floats(n); i += 64) U[i] = 0.f;
+    for (int i = tid; i < L.strips; i += blockDim.x) lds[i] = 0.f;
+    for (int i = lane; i < L.wave; i += 64) U[i] = 0.f;
     __syncthreads();
     for (int i = tid; i < 2 * T * fi * fi; i += blockDim.x) {
         const int c = i % fi, r = (i / fi) % fi, tj = i / (fi * fi), t = tj >> 1, j = tj & 1;
@@ -479,8 +496,6 @@ int bd_blocks(int T, int fi) {                       // 16-column blocks per tow
     return 0;
 }
 
-enum { kBdFwd = 0, kBdBwd = 1, kBdWg = 2, kBdBoth = 3 };
-
 template <int T, int FI>
 hipError_t bd_launch_one(int which, const BdParams& p, int threads, size_t lds, hipStream_t st) {
     static_assert(FI % 2 == 0 && FI % 16 != 0 && T * FI <= 16 * kMaxTiles, "even widths with room for the ones column");
@@ -506,8 +521,6 @@ hipError_t bd_launch(int which, const BdParams& p, int threads, size_t lds, hipS
     return hipErrorInvalidValue;
 }
 
-int bd_max_threads(int which, int T, int FB) { return which == kBdFwd ? bd_fwd_threads(T, FB) : bd_bwd_threads(T, FB); }
-
 int bd_wgrad_groups(int64_t n_rows) {
     const int64_t n_strips = (n_rows + kStrip - 1) / kStrip;
     return (int)std::max<int64_t>(1, std::min<int64_t>(2 * n_cus(), (n_strips + 3) / 4));
@@ -515,25 +528,31 @@ int bd_wgrad_groups(int64_t n_rows) {
 
 // forward / input gradient: persistent workgroups, as many waves per CU as LDS and registers allow
 int bd_launch_stream(const char* fn, int which, BdParams& p, void* stream) {
-    const int FB = bd_blocks(p.T, p.fi);
-    const int k = p.T * p.fi;
-    const size_t w_floats = which == kBdFwd ? (size_t)p.T * 2 * FB * 16 * (16 * FB + 4) + (size_t)p.T * 2 * FB * 16 : (size_t)p.T * FB * 16 * (32 * FB + 4);
-    const size_t wave_floats = which == kBdFwd ? (size_t)kStrip * 2 * k : (size_t)strip_floats(2 * k);
+    const BdLayout L = bd_layout(which, p.T, p.fi);
     // waves per workgroup: the choice that puts the most waves on a CU (LDS: the tiles once per workgroup + a strip per wave)
-    const int max_waves = bd_max_threads(which, p.T, FB) / 64;
+    const int FB = bd_blocks(p.T, p.fi), max_waves = (which == kBdFwd ? bd_fwd_threads(p.T, FB) : bd_bwd_threads(p.T, FB)) / 64;
     int waves = 0, per_cu = 0;
     for (int w = max_waves; w >= 1; --w) {
-        const size_t bytes = (w_floats + w * wave_floats) * 4;
+        const size_t bytes = bd_lds_bytes(L, w);
         if (bytes > (size_t)kLdsBudget) continue;
         const int pc = std::min((int)(kLdsBudget / bytes), 16 / w);
         if (pc * w > per_cu * waves) { waves = w; per_cu = pc; }
     }
     if (!waves) { set_error("%s: operands do not fit in LDS", fn); return -1; }
-    const size_t lds = (w_floats + waves * wave_floats) * 4;
     const int64_t n_strips = (p.M + kStrip - 1) / kStrip;
     p.groups = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)n_cus() * per_cu, (n_strips + waves - 1) / waves));
-    DGN_HIP_CHECK(bd_launch(which, p, waves * 64, lds, static_cast<hipStream_t>(stream)));
+    DGN_HIP_CHECK(bd_launch(which, p, waves * 64, bd_lds_bytes(L, waves), static_cast<hipStream_t>(stream)));
     return 0;
+}
+
+// the slot sums behind the weight-gradient kernels
+int bd_finalize(const BdParams& p, float* dw, int64_t lddw, float* dbias, hipStream_t st) {
+    const int Fm = p.T * p.fi;
+    const int64_t total = (int64_t)2 * Fm * (Fm + 1);
+    hipLaunchKernelGGL(bd_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * wg::kSumWaves), 0, st, p.T, p.fi, bd_blocks(p.T, p.fi), p.groups, p.part, dw,
+                       lddw, dbias);
+    DGN_HIP_CHECK(hipGetLastError());
+    return DGN_OK;
 }
 }  // namespace
 }  // namespace lin
@@ -594,16 +613,9 @@ extern "C" int dgn_linear_bd_wgrad(int64_t n_rows, int32_t n_towers, int32_t f_i
     BdParams p{};
     p.M = n_rows; p.T = n_towers; p.fi = f_in; p.A = g; p.X = x; p.part = static_cast<float*>(ws);
     p.groups = bd_wgrad_groups(n_rows);
-    const int ntl = 2 * n_towers * FB * FB;
-    const size_t lds = std::max((size_t)4 * (strip_floats(2 * Fm) + strip_floats(Fm)), (size_t)ntl * 256) * 4;
-    DGN_HIP_CHECK(bd_launch(kBdWg, p, 256, lds, st));
-    const int64_t total = (int64_t)2 * Fm * (Fm + 1);
-    hipLaunchKernelGGL(bd_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * wg::kSumWaves), 0, st, n_towers, f_in, FB, p.groups, p.part, dw, lddw,
-                       dbias);
-    DGN_HIP_CHECK(hipGetLastError());
-    return DGN_OK;
+    DGN_HIP_CHECK(bd_launch(kBdWg, p, 256, bd_lds_bytes(bd_layout(kBdWg, n_towers, f_in), 256 / 64), st));
+    return bd_finalize(p, dw, lddw, dbias, st);
 }
-
 
 // Input gradient + weight gradient (+ bias gradient) of the block-diagonal product in one pass (bd_backward_both): the arguments of
 // dgn_linear_bd_backward_input and dgn_linear_bd_wgrad together, the workspace of dgn_linear_bd_wgrad_workspace_bytes().  Library-internal
@@ -623,24 +635,19 @@ int bd_backward_both_launch(int64_t n_rows, int32_t n_towers, int32_t f_in, cons
     }
     const size_t need = dgn_linear_bd_wgrad_workspace_bytes(n_rows, n_towers, f_in);
     if (!ws || ws_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, ws_bytes, need); return DGN_ERR_WORKSPACE; }
-    const int ntw = 2 * n_towers * FB * FB;
-    const size_t w_floats = (size_t)n_towers * FB * 16 * (32 * FB + 4), wave_floats = (size_t)strip_floats(2 * Fm) + strip_floats(Fm);
-    int waves = 8;
-    while (waves > 1 && (w_floats + waves * wave_floats) * 4 > (size_t)kLdsBudget) waves /= 2;
-    const size_t lds = std::max((w_floats + waves * wave_floats) * 4, (size_t)ntw * 256 * 4);
-    if (lds > (size_t)kLdsBudget) { set_error("%s: operands do not fit in LDS", fn); return DGN_ERR_INVALID; }
-    const int64_t n_strips = (n_rows + kStrip - 1) / kStrip;
     BdParams p{};
     p.M = n_rows; p.T = n_towers; p.fi = f_in; p.A = g; p.X = x; p.W = w; p.ldw = ldw; p.C = g_h; p.add1 = add1; p.add2 = add2;
     p.part = static_cast<float*>(ws);
+    const BdLayout L = bd_layout(kBdBoth, n_towers, f_in);
+    int waves = 8;
+    while (waves > 1 && bd_lds_bytes(L, waves) > (size_t)kLdsBudget) waves /= 2;
+    const size_t lds = bd_lds_bytes(L, waves);
+    if (lds > (size_t)kLdsBudget) { set_error("%s: operands do not fit in LDS", fn); return DGN_ERR_INVALID; }
+    const int64_t n_strips = (n_rows + kStrip - 1) / kStrip;
     p.groups = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_cus(), bd_wgrad_groups(n_rows)), (n_strips + waves - 1) / waves));
     hipStream_t st = static_cast<hipStream_t>(stream);
     DGN_HIP_CHECK(bd_launch(kBdBoth, p, waves * 64, lds, st));
-    const int64_t total = (int64_t)2 * Fm * (Fm + 1);
-    hipLaunchKernelGGL(bd_wgrad_finalize, dim3((unsigned)((total + 63) / 64)), dim3(64 * wg::kSumWaves), 0, st, n_towers, f_in, FB, p.groups, p.part, dw, lddw,
-                       dbias);
-    DGN_HIP_CHECK(hipGetLastError());
-    return DGN_OK;
+    return bd_finalize(p, dw, lddw, dbias, st);
 }
 }  // namespace lin
 }  // namespace dgn

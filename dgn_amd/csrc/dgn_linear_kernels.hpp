@@ -85,13 +85,16 @@ struct LinParams {
     double* bn_part; int bn_F; int st_off;
 };
 
-// registers a lane needs: accumulators + one block of W operands + the prefetched strip
-constexpr int linear_extra_regs(int KB, int mode) { return mode == 3 ? 12 : (mode == 4 ? 4 * KB + 12 : (mode == 7 ? 2 * KB + 28 : (mode == 8 ? 2 * KB + 28 + 64 : (mode == 5 || mode == 6 ? 64 : 0)))); }    // kBnPlain: column state; kActPlain: a second prefetched strip
-constexpr int linear_threads(int NT, int KB, int mode = 0) {
+enum { kPlain = 0, kCombine = 1, kExpand = 2, kBnPlain = 3, kActPlain = 4, kAddPlain = 5, kMixFwd = 6, kActMask = 7, kActMaskBnb = 8, kLinModes };        // ts_linear variants
+
+// registers a lane needs: accumulators + one block of W operands + the prefetched strip (kBnPlain: column state; kActPlain: a second prefetched strip)
+constexpr int linear_extra_regs(int KB, int mode) { return mode == kBnPlain ? 12 : (mode == kActPlain ? 4 * KB + 12 : (mode == kActMask ? 2 * KB + 28 : (mode == kActMaskBnb ? 2 * KB + 28 + 64 : (mode == kAddPlain || mode == kMixFwd ? 64 : 0)))); }
+constexpr int linear_threads(int NT, int KB, int mode, bool wreg = false) {      // (WREG: 256 registers per lane)
+    if (wreg) return 256;
     const int est = 8 * NT + 4 * KB + 52 + linear_extra_regs(KB, mode);
-    return est <= 116 ? 1024 : (mode == 6 && est <= 180 && NT <= 5 ? 768 : 512);      // (kMixFwd at hidden 65 .. 80: 157 registers, three waves per SIMD)
+    return est <= 116 ? 1024 : (mode == kMixFwd && est <= 180 && NT <= 5 ? 768 : 512);      // (kMixFwd at hidden 65 .. 80: 157 registers, three waves per SIMD)
 }
-__host__ __device__ inline int strip_floats(int k) { return kStrip * k + 16; }     // + slack read by the last row's last block
+__host__ __device__ constexpr int strip_floats(int k) { return kStrip * k + 16; }     // + slack read by the last row's last block
 
 // A strip is 16 * k consecutive floats of A (rows are dense: lda == k) starting at a multiple of 64 bytes: it is copied with
 // 16-byte lanes, float4 number q = jq * 64 + lane living in pre[2 jq], pre[2 jq + 1] (NL = 2 KB is even); the batch's last,
@@ -140,7 +143,6 @@ __device__ __forceinline__ void store_strip(float* Xl, const float2 (&pre)[NL], 
         if (jq * 64 + lane < (kStrip / 4) * k)
             reinterpret_cast<float4*>(Xl)[jq * 64 + lane] = make_float4(pre[2 * jq].x, pre[2 * jq].y, pre[2 * jq + 1].x, pre[2 * jq + 1].y);
 }
-
 
 // "Expanded" strips: the operand is not in memory but G[t][m][s*fo + o] = scale[m][s] * gy[t][m][o] -- the gradient of the
 // posttrans product behind the scale-combine -- formed while the strip is staged.  gy is tower-major, so a strip's 16 * fo
@@ -265,8 +267,6 @@ __device__ __forceinline__ void store_strip_mask(float* Xl, const float2 (&pre)[
     }
 }
 
-enum { kPlain = 0, kCombine = 1, kExpand = 2, kBnPlain = 3, kActPlain = 4, kAddPlain = 5, kMixFwd = 6, kActMask = 7, kActMaskBnb = 8 };        // ts_linear variants
-
 // WREG (round 6): the lane's W operands of ALL 16-k blocks stay in registers (KB x NT f4) instead of being re-read from LDS for every strip --
 // the matrix pipe fed from LDS runs at 95 / 108 / 148 TFLOP/s with one ds_read_b128 per 4 / 8 / 16 MFMAs (profiles/r03_mfma_peak.txt), and
 // the strip products read NT + 1 operands per 4 NT MFMAs (posttrans of the towers: one per 3).  With WREG: one per 4 NT.  Costs the
@@ -274,12 +274,30 @@ enum { kPlain = 0, kCombine = 1, kExpand = 2, kBnPlain = 3, kActPlain = 4, kAddP
 constexpr int kWregTiles = 18;
 // (12 .. 18 tiles; the shapes below need more than the 168 registers of three waves per SIMD -- the build refuses scratch)
 constexpr bool linear_wreg_ok(int NT, int KB, int MODE) {
-    if (!(MODE == 1 || MODE == 2) || NT * KB > kWregTiles || NT * KB < 12) return false;
-    if (MODE == 1) return !(NT == 2 && KB == 9);
+    if (!(MODE == kCombine || MODE == kExpand) || NT * KB > kWregTiles || NT * KB < 12) return false;
+    if (MODE == kCombine) return !(NT == 2 && KB == 9);
     return !((NT == 2 && KB >= 8) || (NT == 3 && KB == 6) || (NT == 9 && KB == 2));
 }
+// ts_linear's dynamic LDS, in floats: [tables][Wl][a strip block per wave] (+ the statistics cells, fp64, behind everything).  The kernel
+// takes its pointers from these functions, launch_linear its byte count and the fit against kLdsBudget from linear_lds_bytes.
+constexpr int linear_tab_floats(int NT, int KB, int mode) {      // Bl [NT*16], Cb [NT*16], Bn: the mode's column tables
+    return 2 * NT * 16 + (mode == kBnPlain || mode == kMixFwd ? 4 * KB * 16 : (mode == kActPlain ? KB * 16 : (mode == kActMaskBnb ? 5 * NT * 16 : 0)));
+}
+__host__ __device__ constexpr int linear_w_floats(int rows, int kp) { return rows * kp; }      // Wl [rows = NT*16][kp]
+// A wave's strip block: Xl (the strip), Cl [16][n], Fl.  A macro, not a function: a function's body is simplified on its own before it is
+// inlined, and the kernels' address arithmetic then comes out in another instruction order than with the sum written in place.
+#define DGN_LIN_WAVE_FLOATS(k, n) (strip_floats(k) + kStrip * (n) + kFacFloats)
+// (LinParams.bn_part: 4 fp64 cells per lane and epilogue trip, per wave)
+__host__ __device__ constexpr int linear_stat_cells(int fo) { return 4 * ((kStrip * (fo >> 1) + 63) >> 6) * 64; }
+// (wreg: the strips lie over the weights, see WREG below; stat_fo: LinParams.fo where bn_part is set, else 0; *st_off: LinParams.st_off)
+inline size_t linear_lds_bytes(int NT, int KB, int mode, bool wreg, int k, int n, int kp, int waves, int stat_fo, int* st_off) {
+    const int w_floats = linear_w_floats(NT * 16, kp), s_floats = waves * DGN_LIN_WAVE_FLOATS(k, n);
+    const int floats = linear_tab_floats(NT, KB, mode) + (wreg ? std::max(w_floats, s_floats) : w_floats + s_floats);
+    *st_off = stat_fo ? floats : 0;                  // (every region is a multiple of 16 floats: the fp64 cells are aligned)
+    return (size_t)floats * 4 + (stat_fo ? (size_t)waves * linear_stat_cells(stat_fo) * sizeof(double) : 0);
+}
 template <int NT, int KB, int MODE, bool WREG = false>
-__global__ __launch_bounds__(WREG ? 256 : linear_threads(NT, KB, MODE), WREG ? 3 : 1) void ts_linear(LinParams p) {
+__global__ __launch_bounds__(linear_threads(NT, KB, MODE, WREG), WREG ? 3 : 1) void ts_linear(LinParams p) {
     constexpr bool COMBINE = MODE == kCombine, EXPAND = MODE == kExpand, MIX = MODE == kMixFwd, BNP = MODE == kBnPlain || MIX, ACT = MODE == kActPlain;
     constexpr bool BNB = MODE == kActMaskBnb, ADD = MODE == kAddPlain || MIX || BNB;      // (BNB: the epilogue's strip-shaped operand is BatchNorm's input)
     constexpr bool ACTM = MODE == kActMask || BNB;
@@ -289,17 +307,17 @@ __global__ __launch_bounds__(WREG ? 256 : linear_threads(NT, KB, MODE), WREG ? 3
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
     const int t = blockIdx.x % p.T, grp = blockIdx.x / p.T;
     const int kp = p.kp, k = p.k, n = p.n;
+    constexpr int kTabFloats = linear_tab_floats(NT, KB, MODE);
     float* Bl = lds;                                 // [NT*16] bias
     float* Cb = Bl + NT * 16;                        // [NT*16] the combine epilogue's bias for this tower
     float* Bn = Cb + NT * 16;                        // kBnPlain: [4][KB*16] mean, invstd, gamma, beta of the operand's columns
-    constexpr int kTabFloats = 2 * NT * 16 + (BNP ? 4 * KB * 16 : (ACT ? KB * 16 : (BNB ? 5 * NT * 16 : 0)));
     float* Wl = lds + kTabFloats;                    // [NT*16][kp], zero beyond (n, k)
     // (WREG: the weights are dead in LDS once every lane holds its operands -- the waves' strips lie over them)
-    float* Xl = (WREG ? Wl : Wl + NT * 16 * kp) + wave * (strip_floats(k) + kStrip * n + kFacFloats);   // this wave's strip, as it lies in memory
+    float* Xl = (WREG ? Wl : Wl + linear_w_floats(NT * 16, kp)) + wave * DGN_LIN_WAVE_FLOATS(k, n);   // this wave's strip, as it lies in memory
     float* Cl = Xl + strip_floats(k);                // results of the previous strip, [16][n]
     float* Fl = Cl + kStrip * n;                     // [2][16][4] per-row factors of the combine epilogue (scale_0..2, row_scale)
     // (LinParams.bn_part: this wave's statistics cells, [4 per epilogue trip][64 lanes] doubles -- each lane's own, the wave's LDS operations run in order)
-    const int st_cells = COMBINE ? 4 * ((kStrip * (p.fo >> 1) + 63) >> 6) * 64 : 0;
+    const int st_cells = COMBINE ? linear_stat_cells(p.fo) : 0;
     double* St = reinterpret_cast<double*>(lds + p.st_off) + wave * st_cells;
     if constexpr (COMBINE) {
         if (p.bn_part) for (int i = lane; i < st_cells; i += 64) St[i] = 0.0;
@@ -335,7 +353,7 @@ __global__ __launch_bounds__(WREG ? 256 : linear_threads(NT, KB, MODE), WREG ? 3
     };
     if (first < n_strips) fetch(first);              // in flight while the weights are set up
 
-    for (int i = tid; i < NT * 16 * kp + kTabFloats; i += blockDim.x) lds[i] = 0.f;
+    for (int i = tid; i < linear_w_floats(NT * 16, kp) + kTabFloats; i += blockDim.x) lds[i] = 0.f;
     __syncthreads();
     const float* Wg = p.W + (int64_t)t * p.sW;
     for (int i = tid; i < n * k; i += blockDim.x) {
@@ -660,6 +678,9 @@ struct WgParams {
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
 constexpr int wgrad_wave_floats(int n, int k, bool gmask) { return strip_floats(n) + strip_floats(k) + 64 + (gmask ? 4 * n : 0); }
+// ts_wgrad's dynamic LDS: the four waves' strips, under the folded [NT*16][KT*16] block at the end; BatchNorm's tables [4][KT*16] behind (WgParams.bn_off)
+constexpr int wgrad_bn_off(int NT, int KT, int n, int k, bool gmask) { return std::max(4 * wgrad_wave_floats(n, k, gmask), NT * 16 * KT * 16); }
+constexpr size_t wgrad_lds_bytes(int NT, int KT, int n, int k, bool gmask, bool bn) { return (size_t)(wgrad_bn_off(NT, KT, n, k, gmask) + (bn ? 4 * KT * 16 : 0)) * 4; }
 // (GMASK at up to 25 accumulator tiles: bounded to the two waves per SIMD the plain kernel reaches on its own -- 254 registers there)
 constexpr int wgrad_min_blocks(int NT, int KT, bool GMASK) { return GMASK && NT == 5 && KT == 5 ? 2 : 1; }      // (hidden 65 .. 80: the shipped widths; 3 x 8 / 8 x 3 would spill)
 template <int NT, int KT, bool EXPAND, bool GMASK = false>
@@ -797,18 +818,16 @@ static __global__ __launch_bounds__(64 * wg::kSumWaves) void ts_wgrad_finalize(i
     }
 }
 
-// ---- dispatch -------------------------------------------------------------------------------------------------
 // ---- dispatch: one translation unit per kernel family (dgn_linear*.hip), each instantiating its (NT, KB) grid --------
-// kActPlain holds two prefetched strips: the widest tile shapes would not fit the registers and are not instantiated
-constexpr bool linear_act_shape_ok(int NT, int KB) { return 4 * NT + 8 * KB <= 104; }
-constexpr bool linear_add_shape_ok(int NT, int KB) { return 16 * NT + 4 * KB <= 128; }      // (kAddPlain: two result-shaped strips per wave in registers)
-constexpr bool linear_bnb_shape_ok(int NT, int KB) { return NT <= 5 && KB <= 7 && NT + KB <= 11; }              // (kActMaskBnb: the unrolled epilogue; wider shapes spill)
-
+// The (NT, KB) shapes instantiated for a mode; the widest ones would not fit the registers where the mode holds
+constexpr bool linear_shape_ok(int NT, int KB, int mode) {
+    return (!(mode == kActPlain || mode == kActMask || mode == kActMaskBnb) || 4 * NT + 8 * KB <= 104) &&      // two prefetched strips
+           (!(mode == kAddPlain || mode == kMixFwd || mode == kActMaskBnb) || 16 * NT + 4 * KB <= 128) &&      // two result-shaped strips per wave in registers
+           (mode != kActMaskBnb || (NT <= 5 && KB <= 7 && NT + KB <= 11));                                      // the unrolled epilogue; wider shapes spill
+}
 template <int NT, int KB, int MODE>
 hipError_t launch_linear_nkm(const LinParams& p, int threads, size_t lds, hipStream_t st) {
-    if constexpr (((MODE == kActPlain || MODE == kActMask || MODE == kActMaskBnb) && !linear_act_shape_ok(NT, KB)) ||
-                  ((MODE == kAddPlain || MODE == kMixFwd || MODE == kActMaskBnb) && !linear_add_shape_ok(NT, KB)) ||
-                  (MODE == kActMaskBnb && !linear_bnb_shape_ok(NT, KB))) {
+    if constexpr (!linear_shape_ok(NT, KB, MODE)) {
         return hipErrorInvalidValue;
     } else {
     if constexpr (linear_wreg_ok(NT, KB, MODE)) {
@@ -876,16 +895,10 @@ hipError_t launch_wgrad_grid(int nt, int kt, const WgParams& p, size_t lds, hipS
     return hipErrorInvalidValue;
 }
 
-// defined in dgn_linear.hip (plain), dgn_linear_combine.hip, dgn_linear_expand.hip, dgn_linear_wgrad.hip
-hipError_t launch_linear_plain(int nt, int kb, const LinParams& p, int threads, size_t lds, hipStream_t st);
-hipError_t launch_linear_combine(int nt, int kb, const LinParams& p, int threads, size_t lds, hipStream_t st);
-hipError_t launch_linear_expand(int nt, int kb, const LinParams& p, int threads, size_t lds, hipStream_t st);
-hipError_t launch_linear_actm(int nt, int kb, const LinParams& p, int threads, size_t lds, hipStream_t st);
-hipError_t launch_linear_bn(int nt, int kb, const LinParams& p, int threads, size_t lds, hipStream_t st);
-hipError_t launch_linear_act(int nt, int kb, const LinParams& p, int threads, size_t lds, hipStream_t st);
-hipError_t launch_linear_add(int nt, int kb, const LinParams& p, int threads, size_t lds, hipStream_t st);
-hipError_t launch_linear_mix(int nt, int kb, const LinParams& p, int threads, size_t lds, hipStream_t st);
-hipError_t launch_linear_bnb(int nt, int kb, const LinParams& p, int threads, size_t lds, hipStream_t st);
+// defined in dgn_linear.hip (plain), dgn_linear_{combine,expand,bn,act,add,mix,actm,bnb}.hip, dgn_linear_wgrad*.hip
+using LinLauncher = hipError_t(int nt, int kb, const LinParams& p, int threads, size_t lds, hipStream_t st);
+LinLauncher launch_linear_plain, launch_linear_combine, launch_linear_expand, launch_linear_bn, launch_linear_act, launch_linear_add, launch_linear_mix,
+    launch_linear_actm, launch_linear_bnb;
 hipError_t launch_wgrad_plain(int nt, int kt, const WgParams& p, size_t lds, hipStream_t st);
 hipError_t launch_wgrad_expand(int nt, int kt, const WgParams& p, size_t lds, hipStream_t st);
 hipError_t launch_wgrad_gmask(int nt, int kt, const WgParams& p, size_t lds, hipStream_t st);

@@ -73,6 +73,12 @@ __device__ __forceinline__ void wave_fold(float* red, float* part, int64_t slot,
 // A 16-row strip of G's and X's columns as 16-byte pieces, gq + xq pieces per row (G's first), dealt to the workgroup's THREADS
 // threads ITEMS at a time: fetched into registers before the current strip's MFMAs, committed to the other LDS buffer after them
 // (dgn_load4.hpp on why the two are apart).  Zero beyond the matrices.
+// The strips' dynamic LDS: two (G strip, X strip) buffers of `rows` rows at the row strides gs, xs (floats); gemm::wgrad_bufs / tw_bufs, dc::wgrad_bufs
+struct StripBufs {
+    int rows, gs, xs;
+    constexpr int half() const { return rows * (gs + xs); }      // floats of one buffer
+    constexpr size_t bytes() const { return (size_t)2 * half() * sizeof(float); }
+};
 struct Strip {
     const float* G; int64_t ldg; int n, g0;      // G [rows, n], the strip's first column
     const float* X; int64_t ldx; int k, x0;

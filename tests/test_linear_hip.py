@@ -252,7 +252,7 @@ def test_wide_linear_autograd_matches_library(monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(4099, 70, 70), (275, 70, 70), (16, 84, 42), (1000, 140, 70), (5, 6, 2)])
+@pytest.mark.parametrize("shape", [(4099, 70, 70), (275, 70, 70), (16, 84, 42), (1000, 140, 70), (5, 6, 2), (40, 160, 160)])
 @pytest.mark.parametrize("affine", [True, False])
 def test_linear_with_batchnorm_prologue_is_bitwise_bn_apply_then_linear(shape, affine):
     """dgn_linear_forward_bn / dgn_linear_wgrad_bn (the operand normalised while its strips are staged) against dgn_bn_tail_forward's
