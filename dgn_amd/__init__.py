@@ -15,10 +15,13 @@ from .eig import laplacian_eigvecs, laplacian_eig_small, laplacian_eig_mid, batc
 from .ops import balanced_cross_entropy, masked_bce_with_logits, mlp_head, multi_embedding
 from .superpixels import coord_encoding, knn_edge_counts, knn_graph, sort_eig, superpixel_eig
 from .nets import AtomEncoder, BondEncoder, DGNHIVNet, DGNNet, DGNNodeNet, DGNPCBANet, accuracy_sbm, ap_ogb, rocauc_ogb
+from .ops import class_cross_entropy, feature_embedding
+from .nets import DGNSuperpixelNet, accuracy_mnist_cifar
 
 __all__ = ["DGNGraph", "as_dgn_graph", "compute_edge_weights", "make_plan", "directional_aggregate", "FCLayer", "MLP",
            "get_activation", "AGGREGATORS", "SCALERS", "DGNLayer", "DGNLayerSimple", "DGNLayerComplex", "DGNLayerTower",
            "DGNTower", "EdgeTypeFeatures", "AGGREGATOR_NAMES", "SCALER_NAMES", "VirtualNode", "sum_nodes", "mean_nodes", "max_nodes", "readout",
            "laplacian_eigvecs", "laplacian_eig_small", "laplacian_eig_mid", "batch_eig", "positional_encoding", "eig_multiplicity", "balanced_cross_entropy", "DGNNet", "DGNNodeNet", "accuracy_sbm",
            "multi_embedding", "masked_bce_with_logits", "mlp_head", "AtomEncoder", "BondEncoder", "DGNHIVNet", "DGNPCBANet", "rocauc_ogb", "ap_ogb",
-           "knn_edge_counts", "knn_graph", "coord_encoding", "sort_eig", "superpixel_eig"]
+           "knn_edge_counts", "knn_graph", "coord_encoding", "sort_eig", "superpixel_eig",
+           "feature_embedding", "class_cross_entropy", "DGNSuperpixelNet", "accuracy_mnist_cifar"]

@@ -299,6 +299,43 @@ class CapturedMolStep(CapturedNetStep):
         return self.net.loss(scores, self.targets)
 
 
+class CapturedSuperpixelStep(CapturedNetStep):
+    """``CapturedNetStep`` for the superpixel graph-classification net (``dgn_amd.nets.DGNSuperpixelNet``: feature embedding, L layers,
+    readout, MLP, cross-entropy with the hit count of ``accuracy_mnist_cifar``, backward, optimizer) -- the same padding scheme and readout
+    CSR, with two changes: the atom buffer is a float ``[n_cap, in_dim]`` feature buffer (zero behind the batch), and the targets are an
+    int64 ``[g_rows]`` label buffer that holds -1 behind the batch, so that the loss kernel itself masks the padding graph rows
+    (``net.loss`` = ``ops.class_cross_entropy``: they count nowhere and their gradient rows are exactly zero).  ``step()`` returns
+    ``(loss, hits)`` device tensors.
+
+    Refused with a ValueError: ``edge_feat=True`` (no static edge-feature buffer): run such a net eagerly."""
+
+    _REFUSED = ((_HAS_EDGE_FEAT, "CapturedSuperpixelStep: nets with edge_feat=True are not supported (no static edge-feature buffer)"),)
+
+    def __init__(self, net, n_cap: int, e_cap: int, g_cap: int, eig_dim: int, **kwargs):
+        super().__init__(net, n_cap, e_cap, g_cap, eig_dim, **kwargs)
+        self.atoms = torch.zeros(self.pb.n_cap, int(net.embedding_h.in_features), device=self.device)
+        self.targets = torch.full((self.g_rows,), -1, dtype=torch.int64, device=self.device)
+        self.hits = torch.zeros((), dtype=torch.int64, device=self.device)
+
+    @torch.no_grad()
+    def load(self, src, dst, num_nodes: int, eig, feats, snorm, sizes, labels) -> None:
+        """feats [num_nodes, in_dim] float32; labels [n_graphs] int64 classes."""
+        G = len(sizes)
+        labels = torch.as_tensor(labels).to(device=self.device, dtype=torch.int64).reshape(G)
+        super().load(src, dst, num_nodes, eig, feats, snorm, sizes, labels)
+        self.targets[G:].fill_(-1)
+
+    def _loss(self, scores: torch.Tensor) -> torch.Tensor:
+        loss, hits = self.net.loss(scores, self.targets, hits=True)
+        self.hits.copy_(hits)
+        return loss
+
+    def step(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One training step on the loaded batch; returns the (device) loss and hit count of that step."""
+        super().step()
+        return self.loss, self.hits
+
+
 class CapturedNodeStep(_CapturedStep):
     """One captured HIP graph for the whole training step of the node-classification net (``dgn_amd.nets.DGNNodeNet``: embedding, L
     layers, per-node MLP, batch-balanced cross-entropy with the confusion matrix of ``accuracy_sbm``, backward, Adam) at a fixed capacity:

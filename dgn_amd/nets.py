@@ -2,7 +2,8 @@
 ``realworld_benchmark/nets/molecules_graph_regression/dgn_net.py:8-95`` (DGNNet) and ``nets/mlp_readout_layer.py:13-32`` (MLPReadout); node
 classification on SBM graphs, ``nets/SBMs_node_classification/dgn_net.py:8-81`` (DGNNodeNet, with ``accuracy_sbm``); graph classification on
 the OGB molecule sets, ``nets/HIV_graph_classification/dgn_net.py`` and ``nets/PCBA_graph_classification/dgn_net.py`` (DGNHIVNet, DGNPCBANet
-with ogb's AtomEncoder / BondEncoder and the evaluator's two metrics, at the end of this file).
+with ogb's AtomEncoder / BondEncoder and the evaluator's two metrics, at the end of this file); graph classification on the MNIST / CIFAR10
+superpixel graphs, ``nets/superpixels_graph_classification/dgn_net.py:7-78`` (DGNSuperpixelNet, with ``accuracy_mnist_cifar``).
 
 Same constructor dictionary, ``forward(g, h, e, snorm_n, snorm_e)``, ``loss`` and ``state_dict`` keys (a reference checkpoint loads
 as is); no DGL call: the layers are ``dgn_amd.DGNLayer``, the readouts ``dgn_amd.readout``, and with ``edge_feat`` the bond-type
@@ -162,7 +163,64 @@ def accuracy_sbm(confusion: torch.Tensor) -> torch.Tensor:
     return 100.0 * recall.sum() / scored.clamp_min(1)     # (no class with a hit: 0 / 1)
 
 
-# ---- OGB molecule nets (ogbg-molhiv, ogbg-molpcba) ----------------------------------------------------------------------------------
+# ---- superpixel graph classification (MNIST, CIFAR10) -------------------------------------------------------------------------------
+
+def _feature_linear(fc: nn.Linear, x: torch.Tensor) -> torch.Tensor:
+    """``fc(x)`` for an input embedding: ``ops.feature_embedding`` where it is supported, ``F.linear`` otherwise (CPU tensors, wider
+    inputs, an ``x`` that asks for a gradient)."""
+    from . import ops
+    if ops.feature_embedding_supported(x, fc.weight):
+        return ops.feature_embedding(x, fc.weight, fc.bias)
+    return F.linear(x, fc.weight, fc.bias)
+
+
+class DGNSuperpixelNet(nn.Module):
+    """Mirror of the reference's superpixel graph-classification net (``nets/superpixels_graph_classification/dgn_net.py:7-78``: MNIST /
+    CIFAR10): ``nn.Linear`` embedding of the node features (mean pixel value(s) + two coordinates), ``L`` DGN layers, sum / max / mean
+    readout (anything else: mean), ``MLPReadout`` to ``n_classes`` scores.  Same constructor dictionary (no ``pos_enc_dim``, no
+    ``device``), ``forward`` signature and ``state_dict`` keys (``embedding_h``, optional ``embedding_e``, ``layers.{i}.*``,
+    ``MLP_layer.FC_layers.{i}.*``); the layers' ``towers`` stays at the factory's default as there.  The embeddings run as
+    ``ops.feature_embedding`` (one launch forward, two backward); with ``edge_feat`` the embedded ``[E, edge_dim]`` rows go to the layers
+    as a dense ``e``.  ``loss`` is ``ops.class_cross_entropy``: two launches, no host read-back, with the hit count of
+    ``accuracy_MNIST_CIFAR`` on request.  Parity: fixture G16 (tests/golden/make_golden_superpixel_net.py), produced by the unmodified net."""
+
+    def __init__(self, net_params: dict):
+        super().__init__()
+        p = net_params
+        hidden, out_dim = p["hidden_dim"], p["out_dim"]
+        self.type_net, self.readout, self.edge_feat, self.n_classes = p["type_net"], p["readout"], p["edge_feat"], p["n_classes"]
+        self.embedding_h = nn.Linear(p["in_dim"], hidden)
+        self.in_feat_dropout = nn.Dropout(p["in_feat_dropout"])
+        if self.edge_feat:
+            self.embedding_e = nn.Linear(p["in_dim_edge"], p["edge_dim"])
+        self.layers = _dgn_layers(p)
+        self.MLP_layer = MLPReadout(out_dim, self.n_classes)
+
+    def forward(self, g, h, e, snorm_n, snorm_e=None):
+        h = self.in_feat_dropout(_feature_linear(self.embedding_h, h))
+        if self.edge_feat:
+            e = _feature_linear(self.embedding_e, e)
+        for conv in self.layers:
+            h = conv(g, h, e, snorm_n)
+        g.ndata["h"] = h
+        return self.MLP_layer(readout(g, h, self.readout if self.readout in ("sum", "max", "mean") else "mean"))
+
+    def loss(self, pred, label, hits: bool = False):
+        """On the device ``label < 0`` marks a padding row.  ``hits=True``: ``(loss, 0-dim int64 count of the correct arg-max predictions)``.
+        CPU tensors: ``F.cross_entropy``, the reference's own call."""
+        if not pred.is_cuda:
+            loss = F.cross_entropy(pred, label)
+            return (loss, accuracy_mnist_cifar(pred, label)) if hits else loss
+        from .ops import class_cross_entropy
+        return class_cross_entropy(pred, label, hits=hits)
+
+
+def accuracy_mnist_cifar(scores: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """The reference's ``accuracy_MNIST_CIFAR`` (train/metrics.py:25-28) without its ``.item()``: the number of rows whose arg-max score
+    sits at the label, a 0-dim int64 tensor on the scores' device (a label < 0 never matches: padding rows count nowhere)."""
+    return (scores.detach().argmax(dim=1) == labels).sum()
+
+
 
 OGB_ATOM_DIMS = [119, 4, 12, 12, 10, 6, 6, 2, 2]      # atomic number, chirality, degree, formal charge, H count, radical e-, hybridisation, aromatic, in ring
 OGB_BOND_DIMS = [5, 6, 2]                             # bond type, stereo, conjugated

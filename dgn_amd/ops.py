@@ -2040,6 +2040,130 @@ def masked_bce_with_logits(scores: torch.Tensor, labels: torch.Tensor) -> torch.
     return _MaskedBCE.apply(scores, labels.to(torch.float32))
 
 
+# ---- superpixel graph classification: feature embedding, class cross-entropy with hit count (dgn_graph_cls.hip) ------------------------
+
+FEAT_EMBED_MAX_K, FEAT_EMBED_MAX_F = _lib.DGN_FEAT_EMBED_MAX_K, _lib.DGN_FEAT_EMBED_MAX_F
+CLASS_CE_MAX_CLASSES = _lib.DGN_CLASS_CE_MAX_CLASSES
+
+
+def feature_embedding_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """Whether ``feature_embedding`` takes ``x [R, K]`` and ``weight [F, K]``: CUDA, fp32, ``K <= 8``, ``F <= 160``, and ``x`` asks for no
+    gradient (the kernels have none to give: the inputs of the net are data)."""
+    return (x.is_cuda and weight.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 2 and weight.dim() == 2
+            and x.shape[1] == weight.shape[1] and 1 <= weight.shape[1] <= FEAT_EMBED_MAX_K and 1 <= weight.shape[0] <= FEAT_EMBED_MAX_F
+            and not x.requires_grad)
+
+
+class _FeatureEmbedding(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        lib = _lib.load()
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        weight = weight.contiguous()
+        bias = bias.contiguous() if bias is not None else None
+        R, K = x.shape
+        F = weight.shape[0]
+        out = torch.empty(R, F, dtype=torch.float32, device=x.device)
+        rc = lib.dgn_feat_embed_forward(R, K, F, x.data_ptr(), x.stride(0) if R > 1 else K, weight.data_ptr(), _ptr(bias), out.data_ptr(), F,
+                                        _lib.stream_ptr(x.device))
+        _lib.check(rc, "dgn_feat_embed_forward")
+        ctx.save_for_backward(x)
+        ctx.F = F
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        (x,) = ctx.saved_tensors
+        R, K = x.shape
+        F, dev = ctx.F, g.device
+        want_b = ctx.needs_input_grad[2]
+        if R == 0:                                            # (the C call launches nothing for no rows: the sums over none)
+            return None, torch.zeros(F, K, device=dev), torch.zeros(F, device=dev) if want_b else None
+        if g.stride(1) != 1:
+            g = g.contiguous()
+        g_w = torch.empty(F, K, dtype=torch.float32, device=dev)
+        g_b = torch.empty(F, dtype=torch.float32, device=dev) if want_b else None
+        ws_bytes = lib.dgn_feat_embed_backward_workspace_bytes(R, K, F)
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
+        rc = lib.dgn_feat_embed_backward(R, K, F, x.data_ptr(), x.stride(0) if R > 1 else K, g.data_ptr(), g.stride(0) if R > 1 else F,
+                                         g_w.data_ptr(), _ptr(g_b), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        _lib.check(rc, "dgn_feat_embed_backward")
+        return None, g_w, g_b
+
+
+def feature_embedding(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``F.linear(x, weight, bias)`` for the input embeddings of the superpixel net (nets/superpixels_graph_classification/dgn_net.py:53,
+    :56): ``x [R, K <= 8]`` fp32 data (any row stride), ``weight [F <= 160, K]``, odd ``F`` included.  One launch forward (every output
+    starts at its bias and takes its ``K`` terms in order), two backward for ``weight.grad`` and ``bias.grad`` (per-workgroup partials,
+    folded in a fixed order: the same bits on every run); no gradient for ``x``.  Shapes outside ``feature_embedding_supported`` raise."""
+    if not x.is_cuda or not weight.is_cuda:
+        raise _lib.DgnError("feature_embedding: CUDA tensors only (dgn_amd has no CPU path)")
+    if not feature_embedding_supported(x, weight):
+        raise ValueError(f"feature_embedding: float32 x [R, K <= {FEAT_EMBED_MAX_K}] without a gradient and weight [F <= {FEAT_EMBED_MAX_F}, K] "
+                         f"required, got {x.dtype} {tuple(x.shape)} / {tuple(weight.shape)}")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (weight.shape[0],)):
+        raise ValueError("feature_embedding: bias must be float32 [F]")
+    return _FeatureEmbedding.apply(x, weight, bias)
+
+
+class _ClassCrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, labels, want_hits, want_grad):
+        lib = _lib.load()
+        if scores.stride(1) != 1:
+            scores = scores.contiguous()
+        labels = labels.contiguous()
+        G, n_classes = scores.shape
+        dev = scores.device
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        hits = torch.empty((), dtype=torch.int64, device=dev) if want_hits else None
+        g = torch.empty(G, n_classes, dtype=torch.float32, device=dev) if want_grad else None
+        ws_bytes = lib.dgn_class_ce_workspace_bytes(G, n_classes)
+        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
+        rc = lib.dgn_class_ce_forward(G, n_classes, scores.data_ptr(), scores.stride(0) if G > 1 else n_classes, labels.data_ptr(), out.data_ptr(),
+                                      _ptr(hits), _ptr(g), n_classes, ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        _lib.check(rc, "dgn_class_ce_forward")
+        ctx.save_for_backward(g)
+        ctx.set_materialize_grads(False)                      # (no zero-filled gradient for the integer count: the backward is ONE launch)
+        loss = out[0]
+        if want_hits:
+            ctx.mark_non_differentiable(hits)
+            return loss, hits
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss, *_):
+        (g,) = ctx.saved_tensors
+        if g_loss is None:
+            return None, None, None, None
+        lib = _lib.load()
+        g_loss = g_loss.to(torch.float32).contiguous()
+        out = torch.empty_like(g)
+        rc = lib.dgn_class_ce_backward(g.shape[0], g.shape[1], g.data_ptr(), g.stride(0), g_loss.data_ptr(), out.data_ptr(), out.stride(0),
+                                       _lib.stream_ptr(g.device))
+        _lib.check(rc, "dgn_class_ce_backward")
+        return out, None, None, None
+
+
+def class_cross_entropy(scores: torch.Tensor, labels: torch.Tensor, hits: bool = False):
+    """``nn.CrossEntropyLoss()(scores, labels)``, the loss of the superpixel net (nets/superpixels_graph_classification/dgn_net.py:75-78):
+    ``scores [G, C]`` float32 with ``2 <= C <= 64`` (any row stride), ``labels [G]`` int64; a label < 0 marks a padding row (counts nowhere,
+    zero gradient).  Two launches, the backward one, no host read-back (capturable).  Returns the 0-dim loss; with ``hits=True`` also the
+    0-dim int64 DEVICE count of the rows whose first maximal score sits at their label -- ``accuracy_MNIST_CIFAR`` (train/metrics.py:25-28)
+    without its ``.item()``.  No valid row: ``nan`` with an all-zero gradient; a label ``>= C`` makes the loss ``nan``."""
+    if not scores.is_cuda or not labels.is_cuda:
+        raise _lib.DgnError("class_cross_entropy: CUDA tensors only (dgn_amd has no CPU path)")
+    if scores.dim() != 2 or scores.dtype != torch.float32 or not 2 <= scores.shape[1] <= CLASS_CE_MAX_CLASSES:
+        raise ValueError(f"class_cross_entropy: scores must be float32 [G, 2 <= C <= {CLASS_CE_MAX_CLASSES}], got {scores.dtype} {tuple(scores.shape)}")
+    if labels.dtype != torch.int64 or labels.shape != (scores.shape[0],):
+        raise ValueError("class_cross_entropy: labels must be int64 [G]")
+    # (whether a gradient is wanted is decided here: inside Function.forward grad mode is always off and needs_input_grad ignores no_grad --
+    #  under torch.no_grad() no [G, C] gradient buffer is allocated or written)
+    return _ClassCrossEntropy.apply(scores, labels, bool(hits), torch.is_grad_enabled() and scores.requires_grad)
+
+
 # ---- the nets' MLPReadout head in one launch per direction (dgn_mlp_head.hip) ---------------------------------------------------------
 
 # The one switch (DGN_FUSED_MLP_HEAD=0 / False: nets.MLPReadout runs its nn.Linear loop on torch's GEMMs): it puts the torch composition

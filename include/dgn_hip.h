@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DGN_ABI_VERSION 34
+#define DGN_ABI_VERSION 35
 
 #define DGN_MAX_AGG 16     /* aggregators per launch (the host splits longer lists)            */
 #define DGN_MAX_CH 4       /* edge-weight channels per launch                                   */
@@ -926,6 +926,55 @@ int dgn_knn_graph(const double* coord, const double* feat, int n_feat, int64_t n
                   int64_t* src, int64_t* dst, float* value, int32_t* status, void* stream);
 int dgn_superpixel_sort_eig(float* eig, int64_t ld_eig, int n_cols, const float* x, const float* y,
                             int64_t n_nodes, const int64_t* graph_off, int n_graphs, void* stream);
+
+/* ---- superpixel graph classification: feature embedding + class cross-entropy with hit count (dgn_graph_cls.hip) ------------------------
+ * Feature embedding.  Replaces embedding_h / embedding_e of nets/superpixels_graph_classification/dgn_net.py:31, :35 as :53, :56 call them:
+ * nn.Linear(in_dim, hidden) on the pixel value(s) + two coordinates (in_dim 3: MNIST, 5: CIFAR10) and nn.Linear(1, edge_dim) on the edge
+ * value -- shapes dgn_linear_supported refuses (odd or tiny k).  x [n_rows, k] fp32 (row stride ld >= k), 1 <= k <= DGN_FEAT_EMBED_MAX_K;
+ * w [f_out, k] dense (torch's layout), 1 <= f_out <= DGN_FEAT_EMBED_MAX_F, odd widths included; b [f_out] or NULL; n_rows < 2^31
+ * (dgn_feat_embed_supported: 1 inside this domain of (k, f_out)).
+ *     forward   y[r, f] = fmaf(w[f, k - 1], x[r, k - 1], ... fmaf(w[f, 0], x[r, 0], b[f])): the terms in increasing k, starting at the bias
+ *               (0 without one).  y [n_rows, f_out] (row stride ld_y >= f_out); dense rows (ld_y == f_out) at a 16-byte aligned base are
+ *               written as flat 16-byte chunks whatever f_out is.  One launch; w and b resident in LDS.
+ *     backward  g_w[f, k] = sum_r g[r, f] x[r, k], g_b[f] = sum_r g[r, f] (g_b: NULL = not wanted); g [n_rows, f_out] (row stride ld_g).
+ *               Two launches: per-workgroup partial [k + 1, f_out] blocks over contiguous row ranges in ws, then the blocks added in a
+ *               fixed order.  No floating-point atomics: the same input gives the same bits.  There is no input gradient: x is data.
+ *               ws: 4-byte aligned, dgn_feat_embed_backward_workspace_bytes bytes (0 for arguments out of range).
+ * n_rows == 0: DGN_OK with nothing launched in either direction; the backward then leaves g_w / g_b as they were (the sum over no row
+ * is the caller's zero fill).
+ *
+ * Class cross-entropy with hit count.  Replaces DGNNet.loss of nets/superpixels_graph_classification/dgn_net.py:75-78
+ * (nn.CrossEntropyLoss(): log_softmax + nll_loss, five small launches forward and two backward) and accuracy_MNIST_CIFAR of
+ * train/metrics.py:25-28 (argmax, eq, sum and the .item() read-back the loop train/train_superpixels_graph_classification.py makes per
+ * step).  scores [n_rows, C] fp32 (row stride ld >= C), 2 <= C <= DGN_CLASS_CE_MAX_CLASSES (dgn_class_ce_supported), labels [n_rows]
+ * int64, n_rows < 2^31.  A label < 0 marks a row that does not exist (padding of a captured batch, as for dgn_node_ce_forward): it counts
+ * nowhere and its gradient row is exactly zero.  V = number of rows with a label >= 0:
+ *     loss      = sum over those rows of (m + log sum_c exp(scores[n, c] - m)) - scores[n, y_n], m = max_c scores[n, c], divided by V
+ *                 DEVICE float; per row in fp32 (exp, log), across rows in fp64 in an order that depends on n_rows alone
+ *     hits      = number of those rows whose FIRST maximal score sits at column y_n (torch.argmax's tie rule; a NaN score counts as
+ *                 the largest, as there).  DEVICE int64; NULL: not wanted
+ *     g_scores  = (softmax(scores[n, :]) - onehot(y_n)) / V   [n_rows, C] (row stride ld_g), every row written; NULL: not wanted
+ * V == 0 (n_rows == 0 included): loss nan (0 / 0, the mean over nothing), hits 0, every gradient row 0.  A label >= C is NOT padding: the
+ * row counts in V, its loss term is nan (so the loss is), it is never a hit, its gradient row is nan, and nothing is read or written
+ * outside the row's C columns.  A NaN score makes the loss nan.  Two launches; ws: 8-byte aligned, dgn_class_ce_workspace_bytes bytes
+ * (0 for arguments out of range).  dgn_class_ce_backward: the autograd backward, ONE launch: g_scores[n, c] = g_saved[n, c] * *g_loss
+ * (g_loss: DEVICE float; g_saved: what the forward wrote). */
+#define DGN_FEAT_EMBED_MAX_K 8
+#define DGN_FEAT_EMBED_MAX_F 160
+#define DGN_CLASS_CE_MAX_CLASSES 64
+int dgn_feat_embed_supported(int32_t k, int32_t f_out);      /* nets/superpixels_graph_classification/dgn_net.py:31, :35 */
+int dgn_feat_embed_forward(int64_t n_rows, int32_t k, int32_t f_out, const float* x, int64_t ld, const float* w, const float* b, float* y,
+                           int64_t ld_y, void* stream);      /* dgn_net.py:53, :56 */
+size_t dgn_feat_embed_backward_workspace_bytes(int64_t n_rows, int32_t k, int32_t f_out);
+int dgn_feat_embed_backward(int64_t n_rows, int32_t k, int32_t f_out, const float* x, int64_t ld, const float* g, int64_t ld_g, float* g_w,
+                            float* g_b, void* ws, size_t ws_bytes, void* stream);      /* autograd of dgn_net.py:53, :56 */
+int dgn_class_ce_supported(int32_t n_classes);
+size_t dgn_class_ce_workspace_bytes(int64_t n_rows, int32_t n_classes);
+int dgn_class_ce_forward(int64_t n_rows, int32_t n_classes, const float* scores, int64_t ld, const int64_t* labels, float* loss,
+                         int64_t* hits, float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes,
+                         void* stream);      /* dgn_net.py:75-78 + train/metrics.py:25-28 */
+int dgn_class_ce_backward(int64_t n_rows, int32_t n_classes, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
+                          int64_t ld_out, void* stream);      /* autograd of dgn_net.py:75-78 */
 
 #ifdef __cplusplus
 }
