@@ -17,6 +17,7 @@ from .superpixels import coord_encoding, knn_edge_counts, knn_graph, sort_eig, s
 from .nets import AtomEncoder, BondEncoder, DGNHIVNet, DGNNet, DGNNodeNet, DGNPCBANet, accuracy_sbm, ap_ogb, rocauc_ogb
 from .ops import class_cross_entropy, feature_embedding
 from .nets import DGNSuperpixelNet, accuracy_mnist_cifar
+from .ops import masked_l1_loss, node_input
 
 __all__ = ["DGNGraph", "as_dgn_graph", "compute_edge_weights", "make_plan", "directional_aggregate", "FCLayer", "MLP",
            "get_activation", "AGGREGATORS", "SCALERS", "DGNLayer", "DGNLayerSimple", "DGNLayerComplex", "DGNLayerTower",
@@ -24,4 +25,5 @@ __all__ = ["DGNGraph", "as_dgn_graph", "compute_edge_weights", "make_plan", "dir
            "laplacian_eigvecs", "laplacian_eig_small", "laplacian_eig_mid", "batch_eig", "positional_encoding", "eig_multiplicity", "balanced_cross_entropy", "DGNNet", "DGNNodeNet", "accuracy_sbm",
            "multi_embedding", "masked_bce_with_logits", "mlp_head", "AtomEncoder", "BondEncoder", "DGNHIVNet", "DGNPCBANet", "rocauc_ogb", "ap_ogb",
            "knn_edge_counts", "knn_graph", "coord_encoding", "sort_eig", "superpixel_eig",
-           "feature_embedding", "class_cross_entropy", "DGNSuperpixelNet", "accuracy_mnist_cifar"]
+           "feature_embedding", "class_cross_entropy", "DGNSuperpixelNet", "accuracy_mnist_cifar",
+           "node_input", "masked_l1_loss"]

@@ -11,6 +11,8 @@
 //   emb_backward_fold     one thread per table element: the workgroups' partials added in workgroup order (fp64), written to table c
 //   bce_stats             one workgroup per contiguous element range: labelled count (integer) and the fp64 sum of the loss terms
 //   bce_rows              every workgroup folds the slots (count, loss), block 0 writes the loss; then the gradient of its range
+//   (both instantiated twice: BceTerm, and L1Term for the masked L1 of the graph-regression net, nets/molecules_graph_regression/
+//    dgn_net.py:90-92 -- dgn_masked_mae_*)
 //   (dgn::scale_rows_async, shared with the node loss: the autograd backward, g_saved * *g_loss)
 //
 // The tables' pointers travel in the kernel arguments (a struct by value): the parameters stay the separate nn.Embedding weights of the
@@ -170,6 +172,25 @@ inline BceLayout bce_layout(int64_t n) {
     return L;
 }
 
+// The per-entry term of a masked mean loss and its gradient (x: score, y: target, not NaN).  nf = (float)count and inv = (float)(1 / count)
+// are both at hand: each term keeps the arithmetic of the loss it replaces.
+struct BceTerm {      // BCEWithLogitsLoss
+    static __device__ __forceinline__ float loss(float xv, float yv) { return (fmaxf(xv, 0.f) - xv * yv) + log1pf(expf(-fabsf(xv))); }
+    static __device__ __forceinline__ float grad(float xv, float yv, float nf, float) {
+        const float e = expf(-fabsf(xv));                        // sigmoid without an overflow at either end
+        const float s = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+        return (s - yv) / nf;
+    }
+};
+struct L1Term {       // L1Loss: |x - y|, gradient sign(x - y) / count with sign(0) = 0 (torch's l1_loss backward)
+    static __device__ __forceinline__ float loss(float xv, float yv) { return fabsf(xv - yv); }
+    static __device__ __forceinline__ float grad(float xv, float yv, float, float inv) {
+        const float d = xv - yv;
+        return d > 0.f ? inv : (d < 0.f ? -inv : 0.f);
+    }
+};
+
+template <class Term>
 __global__ __launch_bounds__(kBceThreads) void bce_stats(int64_t n, int T, const float* __restrict__ x, int64_t ld, const float* __restrict__ y,
                                                           int64_t ld_y, int64_t per, double* __restrict__ lossp, int64_t* __restrict__ cnt) {
     __shared__ double s_red[kBceWaves];
@@ -185,7 +206,7 @@ __global__ __launch_bounds__(kBceThreads) void bce_stats(int64_t n, int T, const
         const int c = (int)(i - r * T);
         const float xv = x[r * ld + c], yv = y[r * ld_y + c];
         if (yv == yv) {                                          // labelled
-            const float term = (fmaxf(xv, 0.f) - xv * yv) + log1pf(expf(-fabsf(xv)));
+            const float term = Term::loss(xv, yv);
             acc += (double)term;
             ++mine;
         }
@@ -195,6 +216,7 @@ __global__ __launch_bounds__(kBceThreads) void bce_stats(int64_t n, int T, const
     if (tid == 0) { lossp[b] = t; cnt[b] = (int64_t)s_cnt; }
 }
 
+template <class Term>
 __global__ __launch_bounds__(kBceThreads) void bce_rows(int64_t n, int T, const float* __restrict__ x, int64_t ld, const float* __restrict__ y,
                                                          int64_t ld_y, int64_t per, int G, const double* __restrict__ lossp,
                                                          const int64_t* __restrict__ cnt, float* __restrict__ loss, float* __restrict__ g,
@@ -210,18 +232,14 @@ __global__ __launch_bounds__(kBceThreads) void bce_rows(int64_t n, int T, const 
     // no labelled entry: 0 / 0 = nan, the mean over an empty selection (train_PCBA_graph_classification.py:32-33)
     if (b == 0 && tid == 0) *loss = (float)(total / (double)labelled);
     if (!g) return;
-    const float nf = (float)labelled;
+    const float nf = (float)labelled, inv = (float)(1.0 / (double)labelled);
     const int64_t e0 = (int64_t)b * per, e1 = (e0 + per < n) ? e0 + per : n;
     for (int64_t i = e0 + tid; i < e1; i += kBceThreads) {
         const int64_t r = i / T;
         const int c = (int)(i - r * T);
         const float xv = x[r * ld + c], yv = y[r * ld_y + c];
         float gv = 0.f;                                          // unlabelled: exactly zero
-        if (yv == yv) {
-            const float e = expf(-fabsf(xv));                    // sigmoid without an overflow at either end
-            const float s = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-            gv = (s - yv) / nf;
-        }
+        if (yv == yv) gv = Term::grad(xv, yv, nf, inv);
         g[r * ld_g + c] = gv;
     }
 }
@@ -317,19 +335,21 @@ extern "C" size_t dgn_masked_bce_workspace_bytes(int64_t n_rows, int32_t n_tasks
     return mol_io::bce_layout(n_rows * n_tasks).bytes;
 }
 
-extern "C" int dgn_masked_bce_forward(int64_t n_rows, int32_t n_tasks, const float* scores, int64_t ld, const float* labels, int64_t ld_y,
-                                      float* loss, float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes, void* stream) {
+// the two launches of a masked mean loss; `who`: the entry point's name for the error text
+template <class Term>
+static int masked_mean_forward(const char* who, int64_t n_rows, int32_t n_tasks, const float* scores, int64_t ld, const float* labels, int64_t ld_y,
+                               float* loss, float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes, void* stream) {
     const int T = n_tasks;
-    if (T < 1) { set_error("dgn_masked_bce_forward: n_tasks >= 1 required (got %d)", T); return DGN_ERR_INVALID; }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_masked_bce_forward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
-    if (!loss) { set_error("dgn_masked_bce_forward: null loss"); return DGN_ERR_INVALID; }
-    if (n_rows > 0 && (!scores || !labels)) { set_error("dgn_masked_bce_forward: null scores / labels"); return DGN_ERR_INVALID; }
-    if (ld < T || ld_y < T || (g_scores && ld_g < T)) { set_error("dgn_masked_bce_forward: row stride below n_tasks"); return DGN_ERR_INVALID; }
+    if (T < 1) { set_error("%s: n_tasks >= 1 required (got %d)", who, T); return DGN_ERR_INVALID; }
+    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("%s: n_rows beyond the int32 range", who); return DGN_ERR_INVALID; }
+    if (!loss) { set_error("%s: null loss", who); return DGN_ERR_INVALID; }
+    if (n_rows > 0 && (!scores || !labels)) { set_error("%s: null scores / labels", who); return DGN_ERR_INVALID; }
+    if (ld < T || ld_y < T || (g_scores && ld_g < T)) { set_error("%s: row stride below n_tasks", who); return DGN_ERR_INVALID; }
     const int64_t n = n_rows * T;
-    if (n > (int64_t)INT32_MAX * 64) { set_error("dgn_masked_bce_forward: n_rows x n_tasks beyond the grid range"); return DGN_ERR_INVALID; }
+    if (n > (int64_t)INT32_MAX * 64) { set_error("%s: n_rows x n_tasks beyond the grid range", who); return DGN_ERR_INVALID; }
     const mol_io::BceLayout L = mol_io::bce_layout(n);
     if (!ws || ws_bytes < L.bytes || (reinterpret_cast<uintptr_t>(ws) & 7)) {
-        set_error("dgn_masked_bce_forward: workspace of %zu bytes (8-byte aligned) required, got %zu", L.bytes, ws_bytes);
+        set_error("%s: workspace of %zu bytes (8-byte aligned) required, got %zu", who, L.bytes, ws_bytes);
         return DGN_ERR_INVALID;
     }
     char* base = static_cast<char*>(ws);
@@ -338,21 +358,47 @@ extern "C" int dgn_masked_bce_forward(int64_t n_rows, int32_t n_tasks, const flo
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)L.groups), block(mol_io::kBceThreads);
     // (no row: the one workgroup finds nothing labelled and the loss is nan, as the mean over an empty selection)
-    hipLaunchKernelGGL(mol_io::bce_stats, grid, block, 0, st, n, T, scores, ld, labels, ld_y, L.per, lossp, cnt);
-    hipLaunchKernelGGL(mol_io::bce_rows, g_scores ? grid : dim3(1), block, 0, st, n, T, scores, ld, labels, ld_y, L.per, L.groups,
+    hipLaunchKernelGGL(mol_io::bce_stats<Term>, grid, block, 0, st, n, T, scores, ld, labels, ld_y, L.per, lossp, cnt);
+    hipLaunchKernelGGL(mol_io::bce_rows<Term>, g_scores ? grid : dim3(1), block, 0, st, n, T, scores, ld, labels, ld_y, L.per, L.groups,
                        (const double*)lossp, (const int64_t*)cnt, loss, g_scores, ld_g);
     DGN_HIP_CHECK(hipGetLastError());
     return DGN_OK;
 }
 
+extern "C" int dgn_masked_bce_forward(int64_t n_rows, int32_t n_tasks, const float* scores, int64_t ld, const float* labels, int64_t ld_y,
+                                      float* loss, float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes, void* stream) {
+    return masked_mean_forward<mol_io::BceTerm>("dgn_masked_bce_forward", n_rows, n_tasks, scores, ld, labels, ld_y, loss, g_scores, ld_g, ws,
+                                                ws_bytes, stream);
+}
+
+static int masked_mean_backward(const char* who, int64_t n_rows, int32_t n_tasks, const float* g_saved, int64_t ld_g, const float* g_loss,
+                                float* g_scores, int64_t ld_out, void* stream) {
+    const int T = n_tasks;
+    if (T < 1) { set_error("%s: n_tasks >= 1 required (got %d)", who, T); return DGN_ERR_INVALID; }
+    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("%s: n_rows beyond the int32 range", who); return DGN_ERR_INVALID; }
+    if (n_rows == 0) return DGN_OK;
+    if (!g_saved || !g_loss || !g_scores) { set_error("%s: null pointer", who); return DGN_ERR_INVALID; }
+    if (ld_g < T || ld_out < T) { set_error("%s: row stride below n_tasks", who); return DGN_ERR_INVALID; }
+    if (n_rows * T > (int64_t)INT32_MAX * 64) { set_error("%s: n_rows x n_tasks beyond the grid range", who); return DGN_ERR_INVALID; }
+    return scale_rows_async(n_rows, T, g_saved, ld_g, g_loss, g_scores, ld_out, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int dgn_masked_bce_backward(int64_t n_rows, int32_t n_tasks, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
                                        int64_t ld_out, void* stream) {
-    const int T = n_tasks;
-    if (T < 1) { set_error("dgn_masked_bce_backward: n_tasks >= 1 required (got %d)", T); return DGN_ERR_INVALID; }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_masked_bce_backward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
-    if (n_rows == 0) return DGN_OK;
-    if (!g_saved || !g_loss || !g_scores) { set_error("dgn_masked_bce_backward: null pointer"); return DGN_ERR_INVALID; }
-    if (ld_g < T || ld_out < T) { set_error("dgn_masked_bce_backward: row stride below n_tasks"); return DGN_ERR_INVALID; }
-    if (n_rows * T > (int64_t)INT32_MAX * 64) { set_error("dgn_masked_bce_backward: n_rows x n_tasks beyond the grid range"); return DGN_ERR_INVALID; }
-    return scale_rows_async(n_rows, T, g_saved, ld_g, g_loss, g_scores, ld_out, static_cast<hipStream_t>(stream));
+    return masked_mean_backward("dgn_masked_bce_backward", n_rows, n_tasks, g_saved, ld_g, g_loss, g_scores, ld_out, stream);
+}
+
+// ---- masked L1 (the graph-regression net's loss): the same two kernels on the L1 term ------------------------------------------------
+
+extern "C" size_t dgn_masked_mae_workspace_bytes(int64_t n_rows, int32_t n_tasks) { return dgn_masked_bce_workspace_bytes(n_rows, n_tasks); }
+
+extern "C" int dgn_masked_mae_forward(int64_t n_rows, int32_t n_tasks, const float* scores, int64_t ld, const float* targets, int64_t ld_y,
+                                     float* loss, float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes, void* stream) {
+    return masked_mean_forward<mol_io::L1Term>("dgn_masked_mae_forward", n_rows, n_tasks, scores, ld, targets, ld_y, loss, g_scores, ld_g, ws,
+                                               ws_bytes, stream);
+}
+
+extern "C" int dgn_masked_mae_backward(int64_t n_rows, int32_t n_tasks, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
+                                      int64_t ld_out, void* stream) {
+    return masked_mean_backward("dgn_masked_mae_backward", n_rows, n_tasks, g_saved, ld_g, g_loss, g_scores, ld_out, stream);
 }

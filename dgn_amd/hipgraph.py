@@ -127,8 +127,23 @@ class _CapturedStep:
         self.net, self.device = net, dev
         self.pb = PaddedBatch(n_cap, e_cap, dev, eig_dim)
         self.snorm = self.pb.add_node_tensor("snorm", 1)
+        # positional encodings: a static [n_cap, K] buffer the net reads from the graph's ndata (rows behind the batch stay zero)
+        self.pos_enc_dim = int(getattr(net, "pos_enc_dim", 0) or 0)
+        if self.pos_enc_dim > 0:
+            self.pb.graph.ndata["pos_enc"] = self.pb.add_node_tensor("pos_enc", self.pos_enc_dim)
         self.loss = torch.zeros((), device=dev)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
+
+    def _node_tensors(self, snorm, pos_enc, who: str) -> dict:
+        """What ``PaddedBatch.load`` copies per node; a net with positional encodings needs ``pos_enc [num_nodes, K]`` and no other takes one."""
+        if (pos_enc is not None) != (self.pos_enc_dim > 0):
+            raise ValueError(f"{who}.load: the net has pos_enc_dim = {self.pos_enc_dim}: " +
+                             ("pass pos_enc [num_nodes, pos_enc_dim]" if pos_enc is None else "it takes no pos_enc"))
+        if pos_enc is None:
+            return {"snorm": snorm}
+        if pos_enc.dim() != 2 or pos_enc.shape[1] != self.pos_enc_dim:
+            raise ValueError(f"{who}.load: pos_enc must be [num_nodes, {self.pos_enc_dim}], got {tuple(pos_enc.shape)}")
+        return {"snorm": snorm, "pos_enc": pos_enc}
 
     def _set_optimizer(self, optimizer, lr: float) -> None:
         """The last act of a constructor (a refused construction leaves the net's Parameter objects alone)."""
@@ -167,7 +182,11 @@ class CapturedNetStep(_CapturedStep):
 
     Padding: node rows beyond the batch are isolated (``PaddedBatch``); graph rows beyond the batch are empty, and the padding nodes
     are shared out among the last PAD_ROWS graph rows, whose loss terms are masked -- every slot of the readout CSR stays referenced, so its backward defines
-    (zero) gradients for the padding rows.  The loss is the mean absolute error over the real graphs (``nets.DGNNet.loss``).
+    (zero) gradients for the padding rows.  The loss is the mean absolute error over the real graphs (``nets.DGNNet.loss`` =
+    ``ops.masked_l1_loss``: the target buffer holds NaN behind the batch and the loss kernel itself masks those rows).
+
+    A net with ``pos_enc_dim > 0`` reads its positional encodings from a static ``[n_cap, pos_enc_dim]`` buffer placed once in the padded
+    graph's ``ndata['pos_enc']`` (zero behind the batch); ``load(..., pos_enc=eig[:, 1:K+1])`` fills it.
 
     An ``optimizer`` passed in must be capturable (``capturable=True`` for Adam-type optimizers; plain SGD is) and must have been built
     on parameters that never took part in a default-stream autograd pass (``rewrap_parameters`` first).  Unless an ``optimizer`` is
@@ -193,12 +212,9 @@ class CapturedNetStep(_CapturedStep):
         if max_graph_nodes and max_graph_edges:
             self.pb.graph.set_block_capacity(g_cap, max_graph_nodes, max_graph_edges)
         self.atoms = torch.zeros(n_cap, dtype=torch.int64, device=dev)
-        self.targets = torch.zeros(g_cap, 1, device=dev)
-        self.gmask = torch.zeros(g_cap, 1, device=dev)
-        self.n_graphs = torch.ones(1, device=dev)
+        self.targets = torch.full((g_cap, 1), float("nan"), device=dev)      # NaN behind the batch: the loss kernel masks those rows
         self._h_sizes = torch.zeros(g_cap, dtype=torch.int64).pin_memory()
         self._d_sizes = torch.zeros(g_cap, dtype=torch.int64, device=dev)
-        self._g_ids = torch.arange(g_cap, device=dev).unsqueeze(1)
         # the readout's CSR: rows = graphs (the last one collects the padding nodes), slots = nodes in order
         # (built from an even split: no row may look like a hub row -- more than 2048 slots -- at construction, the hub description of
         #  a DGNGraph is static)
@@ -217,9 +233,17 @@ class CapturedNetStep(_CapturedStep):
         self._set_optimizer(optimizer, lr)
 
     @torch.no_grad()
-    def load(self, src, dst, num_nodes: int, eig, atoms, snorm, sizes, targets) -> None:
-        """sizes: nodes per graph (host list or tensor), targets [n_graphs, 1]."""
+    def load(self, src, dst, num_nodes: int, eig, atoms, snorm, sizes, targets, pos_enc=None) -> None:
+        """sizes: nodes per graph (host list or tensor), targets [n_graphs, 1]; pos_enc [num_nodes, pos_enc_dim] (any strides: the
+        ``eig[:, 1:K+1]`` slice as it is) for a net with positional encodings, None for every other."""
+        self._load_batch(src, dst, num_nodes, eig, atoms, snorm, sizes, targets, pos_enc)
+        self.targets[len(sizes):].fill_(float("nan"))             # (the subclasses write their own marker: their load calls _load_batch)
+
+    @torch.no_grad()
+    def _load_batch(self, src, dst, num_nodes: int, eig, atoms, snorm, sizes, targets, pos_enc=None) -> None:
+        """``load`` without the marker behind the batch's target rows."""
         n_cap, g_cap, dev = self.pb.n_cap, self.g_rows, self.device
+        node = self._node_tensors(snorm, pos_enc, type(self).__name__)
         sizes = torch.as_tensor(sizes, dtype=torch.int64)
         G = sizes.numel()
         if G >= self.g_cap:
@@ -227,7 +251,7 @@ class CapturedNetStep(_CapturedStep):
         pad, R = n_cap - int(num_nodes), self.PAD_ROWS
         if pad > 2048 * R:
             raise ValueError(f"more than {2048 * R} padding nodes: pick a smaller capacity bucket (a padding row must not be a hub row)")
-        self.pb.load(src, dst, num_nodes, eig, node={"snorm": snorm}, graph_sizes=sizes)
+        self.pb.load(src, dst, num_nodes, eig, node=node, graph_sizes=sizes)
         self.atoms[:num_nodes].copy_(atoms, non_blocking=True)
         self.atoms[num_nodes:].zero_()
         # graph sizes -> the readout CSR, on the device: ONE copy from a pinned staging buffer (a pageable host tensor copied
@@ -242,10 +266,7 @@ class CapturedNetStep(_CapturedStep):
         rg.indptr[1:].copy_(torch.cumsum(self._d_sizes, 0))
         rg.in_degree.copy_(self._d_sizes)
         rg.log_deg.copy_(torch.log((self._d_sizes + 1).double()))
-        self.targets.zero_()
         self.targets[:G].copy_(targets, non_blocking=True)
-        self.gmask.copy_((self._g_ids < G).to(self.gmask.dtype))
-        self.n_graphs.fill_(float(G))
 
     def _step(self) -> None:
         self.opt.zero_grad(set_to_none=True)
@@ -261,8 +282,8 @@ class CapturedNetStep(_CapturedStep):
         del scores, loss
 
     def _loss(self, scores: torch.Tensor) -> torch.Tensor:
-        """The net's loss over the real graph rows (mean absolute error; the rows behind the batch are masked)."""
-        return ((scores - self.targets).abs() * self.gmask).sum() / self.n_graphs
+        """The net's loss over the real graph rows (mean absolute error; the NaN targets behind the batch mask their rows)."""
+        return self.net.loss(scores, self.targets)
 
 
 class CapturedMolStep(CapturedNetStep):
@@ -292,7 +313,7 @@ class CapturedMolStep(CapturedNetStep):
         """atoms [num_nodes, 9] int64; labels [n_graphs] or [n_graphs, n_tasks] of any dtype, NaN = not measured."""
         G = len(sizes)
         labels = torch.as_tensor(labels).to(device=self.device, dtype=torch.float32).reshape(G, -1)
-        super().load(src, dst, num_nodes, eig, atoms, snorm, sizes, labels)
+        self._load_batch(src, dst, num_nodes, eig, atoms, snorm, sizes, labels)
         self.targets[G:].fill_(float("nan"))
 
     def _loss(self, scores: torch.Tensor) -> torch.Tensor:
@@ -322,7 +343,7 @@ class CapturedSuperpixelStep(CapturedNetStep):
         """feats [num_nodes, in_dim] float32; labels [n_graphs] int64 classes."""
         G = len(sizes)
         labels = torch.as_tensor(labels).to(device=self.device, dtype=torch.int64).reshape(G)
-        super().load(src, dst, num_nodes, eig, feats, snorm, sizes, labels)
+        self._load_batch(src, dst, num_nodes, eig, feats, snorm, sizes, labels)
         self.targets[G:].fill_(-1)
 
     def _loss(self, scores: torch.Tensor) -> torch.Tensor:
@@ -343,12 +364,12 @@ class CapturedNodeStep(_CapturedStep):
 
     Padding: node rows beyond the batch are isolated (``PaddedBatch``) and carry the label -1 -- the loss kernel counts them nowhere and
     writes zero gradient rows for them, which is the zero cotangent ``PaddedBatch`` asks for; no readout CSR and no graph rows are needed.
+    A net with ``pos_enc_dim > 0`` gets a static ``[n_cap, pos_enc_dim]`` buffer in ``ndata['pos_enc']``, filled by ``load(..., pos_enc=...)``.
 
     ``optimizer``: as for ``CapturedNetStep`` (capturable, built on parameters that never took part in a default-stream autograd pass);
     by default the net's Parameter objects are re-created (``rewrap_parameters``) and a capturable Adam is built on them."""
 
-    _REFUSED = ((_HAS_EDGE_FEAT, "CapturedNodeStep: nets with edge_feat=True are not supported (no static edge-feature buffer)"),
-                (_HAS_POS_ENC, "CapturedNodeStep: nets with pos_enc_dim > 0 are not supported (no static positional-encoding buffer)"))
+    _REFUSED = ((_HAS_EDGE_FEAT, "CapturedNodeStep: nets with edge_feat=True are not supported (no static edge-feature buffer)"),)
 
     def __init__(self, net, n_cap: int, e_cap: int, eig_dim: int, lr: float = 1e-3, optimizer=None, device=None):
         super().__init__(net, n_cap, e_cap, eig_dim, device)
@@ -360,10 +381,11 @@ class CapturedNodeStep(_CapturedStep):
         self._set_optimizer(optimizer, lr)
 
     @torch.no_grad()
-    def load(self, src, dst, num_nodes: int, eig, feats, snorm, labels, sizes=None) -> None:
-        """feats [num_nodes] int64 node types, labels [num_nodes] int64 classes; sizes: nodes per graph (only for a graph with a block table)."""
+    def load(self, src, dst, num_nodes: int, eig, feats, snorm, labels, sizes=None, pos_enc=None) -> None:
+        """feats [num_nodes] int64 node types, labels [num_nodes] int64 classes; sizes: nodes per graph (only for a graph with a block table);
+        pos_enc [num_nodes, pos_enc_dim] (any strides) for a net with positional encodings, None for every other."""
         num_nodes = int(num_nodes)
-        self.pb.load(src, dst, num_nodes, eig, node={"snorm": snorm}, graph_sizes=sizes)
+        self.pb.load(src, dst, num_nodes, eig, node=self._node_tensors(snorm, pos_enc, "CapturedNodeStep"), graph_sizes=sizes)
         self.feats[:num_nodes].copy_(feats, non_blocking=True)
         self.feats[num_nodes:].zero_()
         self.labels[:num_nodes].copy_(labels, non_blocking=True)

@@ -70,6 +70,27 @@ def small_table_embedding(emb: nn.Embedding, idx: torch.Tensor) -> torch.Tensor:
     return emb(idx)
 
 
+def _input_with_pos_enc(net: nn.Module, tables, idx: torch.Tensor, embed, g) -> torch.Tensor:
+    """``h = in_feat_dropout(embedding_h(h)) + embedding_pos_enc(g.ndata['pos_enc'])`` (nets/molecules_graph_regression/dgn_net.py:59-62,
+    nets/SBMs_node_classification/dgn_net.py:56-59, nets/HIV_graph_classification/dgn_net.py:62-66).  The dropout acts on the embedding
+    before the add, so the two terms are fused -- ``ops.node_input``: one launch forward, two backward -- only while it is inactive
+    (``p == 0`` or ``eval()``) and the op supports the shapes; otherwise the composition: ``embed(idx)``, ``nn.Linear``, add.  ``tables``:
+    the plain embedding weights behind ``embed``, or None where the module is no plain lookup."""
+    from . import ops
+    pe = g.ndata["pos_enc"].to(idx.device)
+    fc, drop = net.embedding_pos_enc, net.in_feat_dropout
+    if (tables is not None and idx.is_cuda and not (drop.training and drop.p > 0) and idx.dtype == torch.int64
+            and ops.node_input_supported(tables, pe, fc.weight)):
+        return ops.node_input(idx, tables, pe, fc.weight, fc.bias)
+    return drop(embed(idx)) + fc(pe)
+
+
+def _plain_table(emb: nn.Embedding):
+    """``[emb.weight]`` for an embedding that is nothing but a lookup (what ``ops.node_input`` fuses), else None."""
+    plain = emb.padding_idx is None and emb.max_norm is None and not emb.sparse and not emb.scale_grad_by_freq
+    return [emb.weight] if plain else None
+
+
 def _dgn_layers(p: dict, towers=None) -> nn.ModuleList:
     """The nets' layer stack from the constructor dictionary: ``L - 1`` layers ``hidden_dim -> hidden_dim`` and one to ``out_dim``, created
     in that order (the order of the initialisation's RNG draws); ``towers=None`` leaves the layer factory's default."""
@@ -100,9 +121,11 @@ class DGNNet(nn.Module):
         self.MLP_layer = MLPReadout(2 * out_dim if directional else out_dim, 1)
 
     def forward(self, g, h, e, snorm_n, snorm_e=None):
-        h = self.in_feat_dropout(small_table_embedding(self.embedding_h, h))
         if self.pos_enc_dim > 0:
-            h = h + self.embedding_pos_enc(g.ndata["pos_enc"].to(h.device))
+            h = _input_with_pos_enc(self, _plain_table(self.embedding_h) if h.dim() == 1 else None, h,
+                                    lambda idx: small_table_embedding(self.embedding_h, idx), g)
+        else:
+            h = self.in_feat_dropout(small_table_embedding(self.embedding_h, h))
         if self.edge_feat:
             e = EdgeTypeFeatures(self.embedding_e.weight, e)
         for conv in self.layers:
@@ -112,6 +135,11 @@ class DGNNet(nn.Module):
         return self.MLP_layer(readout(g, h, mode))
 
     def loss(self, scores, targets):
+        """``nn.L1Loss()`` (dgn_net.py:90-92).  On the device it is ``ops.masked_l1_loss``: two launches forward and one backward, and a
+        NaN target marks an entry that does not count (the graph rows behind the batch of a captured step)."""
+        if scores.is_cuda and targets.is_cuda and scores.dtype == torch.float32 and scores.shape == targets.shape and scores.dim() in (1, 2):
+            from .ops import masked_l1_loss
+            return masked_l1_loss(scores, targets)
         return F.l1_loss(scores, targets)
 
 
@@ -138,9 +166,11 @@ class DGNNodeNet(nn.Module):
         self.MLP_layer = MLPReadout(out_dim, self.n_classes)
 
     def forward(self, g, h, e, snorm_n, snorm_e=None):
-        h = self.in_feat_dropout(small_table_embedding(self.embedding_h, h))
         if self.pos_enc_dim > 0:
-            h = h + self.embedding_pos_enc(g.ndata["pos_enc"].to(h.device))
+            h = _input_with_pos_enc(self, _plain_table(self.embedding_h) if h.dim() == 1 else None, h,
+                                    lambda idx: small_table_embedding(self.embedding_h, idx), g)
+        else:
+            h = self.in_feat_dropout(small_table_embedding(self.embedding_h, h))
         for conv in self.layers:
             h = conv(g, h, e, snorm_n)
         return self.MLP_layer(h)
@@ -339,9 +369,10 @@ class _DGNMolNet(nn.Module):
                                                                   vn_type=virtual_node, residual=p["residual"]) for _ in range(n_layers - 1)])
 
     def forward(self, g, h, e, snorm_n, snorm_e=None):
-        h = self.in_feat_dropout(self.embedding_h(h))
         if self.pos_enc_dim > 0:
-            h = h + self.embedding_pos_enc(g.ndata["pos_enc"].to(h.device))
+            h = _input_with_pos_enc(self, self.embedding_h.weights if h.dim() == 2 else None, h, self.embedding_h, g)
+        else:
+            h = self.in_feat_dropout(self.embedding_h(h))
         if self.edge_feat:
             e = self.embedding_e.edge_type_features(e, g if hasattr(g, "__dict__") else None)
         vn_h = 0

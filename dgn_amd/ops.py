@@ -2040,6 +2040,153 @@ def masked_bce_with_logits(scores: torch.Tensor, labels: torch.Tensor) -> torch.
     return _MaskedBCE.apply(scores, labels.to(torch.float32))
 
 
+class _MaskedL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, targets):
+        lib = _lib.load()
+        if scores.stride(1) != 1:
+            scores = scores.contiguous()
+        targets = targets.contiguous()
+        G, T = scores.shape
+        dev = scores.device
+        want_grad = ctx.needs_input_grad[0]                   # (False under torch.no_grad(): no gradient buffer is written)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        g = torch.empty(G, T, dtype=torch.float32, device=dev) if want_grad else None
+        ws_bytes = lib.dgn_masked_mae_workspace_bytes(G, T)
+        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
+        rc = lib.dgn_masked_mae_forward(G, T, scores.data_ptr(), scores.stride(0) if G > 1 else T, targets.data_ptr(), T, out.data_ptr(), _ptr(g), T,
+                                       ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        _lib.check(rc, "dgn_masked_mae_forward")
+        ctx.save_for_backward(g)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        (g,) = ctx.saved_tensors
+        lib = _lib.load()
+        g_loss = g_loss.to(torch.float32).contiguous()
+        out = torch.empty_like(g)
+        rc = lib.dgn_masked_mae_backward(g.shape[0], g.shape[1], g.data_ptr(), g.stride(0), g_loss.data_ptr(), out.data_ptr(), out.stride(0),
+                                        _lib.stream_ptr(g.device))
+        _lib.check(rc, "dgn_masked_mae_backward")
+        return out, None
+
+
+def masked_l1_loss(scores: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    """The mean of ``|scores - targets|`` over the entries whose target is not NaN (the convention of ``masked_bce_with_logits``): with no
+    NaN it is ``nn.L1Loss()`` of the graph-regression net (nets/molecules_graph_regression/dgn_net.py:90-92) and ``MAE`` of
+    train/metrics.py:14-16; the NaN rows are how a captured step marks the graph rows behind its batch.  Two launches (the count taken on
+    the device, the fp64 sum of the fp32 terms, the gradient ``sign(s - t) / count`` written in the same pass when one is wanted), one
+    launch backward.  ``scores`` float32 ``[G, T]`` or ``[G]`` of any row stride, ``targets`` of the same shape and any dtype.  No counted
+    entry gives ``nan`` with an all-zero gradient."""
+    if not scores.is_cuda or not targets.is_cuda:
+        raise _lib.DgnError("masked_l1_loss: CUDA tensors only (dgn_amd has no CPU path)")
+    shape = scores.shape
+    if scores.dim() == 1:
+        scores, targets = scores.unsqueeze(-1), targets.unsqueeze(-1)
+    if scores.dim() != 2 or scores.dtype != torch.float32 or targets.shape != scores.shape:
+        raise ValueError(f"masked_l1_loss: float32 scores [G, T] and targets of the same shape, got {scores.dtype} {tuple(shape)} / "
+                         f"{tuple(targets.shape)}")
+    if scores.shape[1] == 0:
+        raise ValueError("masked_l1_loss: at least one target column")
+    return _MaskedL1.apply(scores, targets.to(torch.float32))
+
+
+# ---- input stage with positional encodings: embedding sum + Linear on pos_enc (dgn_node_input.hip) ---------------------------------------
+
+NODE_INPUT_MAX_K = _lib.DGN_NODE_INPUT_MAX_K
+
+
+def node_input_supported(tables, pos_enc: torch.Tensor, weight: torch.Tensor) -> bool:
+    """Whether ``node_input`` runs the fused kernels: CUDA fp32 tables ``[dims[c], F]`` (at most 16), ``pos_enc [N, K]`` fp32 with unit
+    column stride that asks for no gradient (the kernels have none to give: it is data), ``weight [F, K]`` with ``K <= 40``, and the
+    backward's ``(sum(dims) + K + 1) x F`` block within the LDS budget (dgn_node_input_supported)."""
+    tables = tuple(tables)
+    if not 1 <= len(tables) <= MULTI_EMBEDDING_MAX_COLS or weight.dim() != 2 or pos_enc.dim() != 2:
+        return False
+    F, K = int(weight.shape[0]), int(weight.shape[1])
+    if not (pos_enc.is_cuda and weight.is_cuda and pos_enc.dtype == torch.float32 and weight.dtype == torch.float32
+            and pos_enc.shape[1] == K and 1 <= K <= NODE_INPUT_MAX_K and not pos_enc.requires_grad):
+        return False
+    if any(not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != F for t in tables):
+        return False
+    dims = [int(t.shape[0]) for t in tables]
+    return bool(_lib.load().dgn_node_input_supported(len(dims), _i32_array(dims), K, F))
+
+
+class _NodeInput(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, idx, pos_enc, weight, bias, *tables):
+        lib = _lib.load()
+        N, n_cols = idx.shape
+        F, K = weight.shape
+        tables = tuple(t.contiguous() for t in tables)
+        weight = weight.contiguous()
+        bias = bias.contiguous() if bias is not None else None
+        if idx.stride(1) != 1:
+            idx = idx.contiguous()
+        if pos_enc.stride(1) != 1:
+            pos_enc = pos_enc.contiguous()
+        dims = _i32_array([int(t.shape[0]) for t in tables])
+        out = torch.empty(N, F, dtype=torch.float32, device=idx.device)
+        rc = lib.dgn_node_input_forward(N, n_cols, K, F, idx.data_ptr(), idx.stride(0) if N > 1 else n_cols, _ptr_array(tables), dims,
+                                        pos_enc.data_ptr(), pos_enc.stride(0) if N > 1 else K, weight.data_ptr(), _ptr(bias), out.data_ptr(), F,
+                                        _lib.stream_ptr(idx.device))
+        _lib.check(rc, "dgn_node_input_forward")
+        ctx.save_for_backward(idx, pos_enc)
+        ctx.dims, ctx.F, ctx.K = dims, F, K
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        idx, pos_enc = ctx.saved_tensors
+        N, n_cols = idx.shape
+        F, K, dims, dev = ctx.F, ctx.K, ctx.dims, g.device
+        want_b = ctx.needs_input_grad[3]
+        new = torch.zeros if N == 0 else torch.empty          # (the C call launches nothing for no rows: the sums over none)
+        grads = [new(int(d), F, dtype=torch.float32, device=dev) for d in dims]
+        g_w = new(F, K, dtype=torch.float32, device=dev)
+        g_b = new(F, dtype=torch.float32, device=dev) if want_b else None
+        if N > 0:
+            if g.stride(1) != 1:
+                g = g.contiguous()
+            ws_bytes = lib.dgn_node_input_backward_workspace_bytes(N, n_cols, dims, K, F)
+            ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
+            rc = lib.dgn_node_input_backward(N, n_cols, K, F, idx.data_ptr(), idx.stride(0) if N > 1 else n_cols, dims, pos_enc.data_ptr(),
+                                             pos_enc.stride(0) if N > 1 else K, g.data_ptr(), g.stride(0) if N > 1 else F, _ptr_array(grads),
+                                             g_w.data_ptr(), _ptr(g_b), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+            _lib.check(rc, "dgn_node_input_backward")
+        need = ctx.needs_input_grad
+        return (None, None, g_w if need[2] else None, g_b) + tuple(gr if n else None for gr, n in zip(grads, need[4:]))
+
+
+def node_input(idx: torch.Tensor, tables, pos_enc: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``sum_c tables[c][idx[:, c]] + F.linear(pos_enc, weight, bias)`` -- the input stage of the nets with positional encodings
+    (nets/molecules_graph_regression/dgn_net.py:60-62, nets/SBMs_node_classification/dgn_net.py:57-59, nets/HIV_graph_classification/
+    dgn_net.py:64-66, with ``in_feat_dropout`` inactive) as ONE launch forward and two backward for every table's, the weight's and the
+    bias' gradient (one pass over the upstream gradient, no floating-point atomics: the same bits on every run).  ``idx`` int64 ``[N]``
+    (one table) or ``[N, C]``; ``tables``: the ``nn.Embedding`` weights, fp32 ``[dims[c], F]``; ``pos_enc`` fp32 ``[N, K <= 40]`` of any
+    row stride and alignment (``eig[:, 1:K+1]`` as it is); ``weight [F, K]``.  No gradient for ``pos_enc``.  An index outside its table is
+    clamped.  Shapes outside ``node_input_supported`` raise: the nets take the composition there."""
+    tables = tuple(tables)
+    if not idx.is_cuda or not pos_enc.is_cuda or not weight.is_cuda or not all(t.is_cuda for t in tables):
+        raise _lib.DgnError("node_input: CUDA tensors only (dgn_amd has no CPU path)")
+    if idx.dim() == 1:
+        idx = idx.unsqueeze(-1)
+    if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[1] != len(tables):
+        raise ValueError(f"node_input: idx must be int64 [N] or [N, {len(tables)}], got {idx.dtype} {tuple(idx.shape)}")
+    if not node_input_supported(tables, pos_enc, weight):
+        raise ValueError(f"node_input: not supported -- float32 tables [dims[c], F], pos_enc [N, K <= {NODE_INPUT_MAX_K}] without a gradient and "
+                         f"weight [F, K] within the LDS budget required (node_input_supported), got pos_enc {pos_enc.dtype} "
+                         f"{tuple(pos_enc.shape)} / weight {tuple(weight.shape)}")
+    if pos_enc.shape[0] != idx.shape[0]:
+        raise ValueError(f"node_input: {idx.shape[0]} index rows but {pos_enc.shape[0]} pos_enc rows")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (weight.shape[0],)):
+        raise ValueError("node_input: bias must be float32 [F]")
+    return _NodeInput.apply(idx, pos_enc, weight, bias, *tables)
+
+
 # ---- superpixel graph classification: feature embedding, class cross-entropy with hit count (dgn_graph_cls.hip) ------------------------
 
 FEAT_EMBED_MAX_K, FEAT_EMBED_MAX_F = _lib.DGN_FEAT_EMBED_MAX_K, _lib.DGN_FEAT_EMBED_MAX_F

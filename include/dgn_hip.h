@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DGN_ABI_VERSION 35
+#define DGN_ABI_VERSION 36
 
 #define DGN_MAX_AGG 16     /* aggregators per launch (the host splits longer lists)            */
 #define DGN_MAX_CH 4       /* edge-weight channels per launch                                   */
@@ -835,6 +835,19 @@ int dgn_masked_bce_forward(int64_t n_rows, int32_t n_tasks, const float* scores,
                            float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes, void* stream);
 int dgn_masked_bce_backward(int64_t n_rows, int32_t n_tasks, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
                             int64_t ld_out, void* stream);
+/* Masked L1.  Replaces nn.L1Loss() of nets/molecules_graph_regression/dgn_net.py:90-92 (= MAE of train/metrics.py:14-16) with the masking
+ * convention above: targets [G, T] fp32 (row stride ld_y), NaN = the entry does not count (a padding graph row of a captured batch).  The
+ * same two kernels on another term, the same workspace and launch counts:
+ *     loss      = (float)(sum over the counted entries of |x - t| (fp32 terms, fp64 sum) / count)     DEVICE float; no counted entry: nan
+ *     g_scores  = sign(x - t) * (float)(1.0 / (double)count) on counted entries (sign(0) = 0, as torch's l1_loss backward), exactly 0
+ *                 elsewhere; NULL: not wanted
+ * dgn_masked_mae_backward: the autograd backward, ONE launch: g_scores[r, t] = g_saved[r, t] * *g_loss.  (The entry points are named after
+ * the metric, mean absolute error: the binding's symbol check reads names of letters and underscores.)                                */
+size_t dgn_masked_mae_workspace_bytes(int64_t n_rows, int32_t n_tasks);
+int dgn_masked_mae_forward(int64_t n_rows, int32_t n_tasks, const float* scores, int64_t ld, const float* targets, int64_t ld_y, float* loss,
+                          float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes, void* stream);      /* dgn_net.py:90-92 */
+int dgn_masked_mae_backward(int64_t n_rows, int32_t n_tasks, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
+                           int64_t ld_out, void* stream);      /* autograd of dgn_net.py:90-92 */
 
 /* ---- the nets' MLP head in one launch per direction (dgn_mlp_head.hip) ---------------------------------------------------------------
  * Replaces MLPReadout.forward of nets/mlp_readout_layer.py:24-30 (L hidden Linear + ReLU, then an output Linear: three addmm and two ReLU
@@ -975,6 +988,38 @@ int dgn_class_ce_forward(int64_t n_rows, int32_t n_classes, const float* scores,
                          void* stream);      /* dgn_net.py:75-78 + train/metrics.py:25-28 */
 int dgn_class_ce_backward(int64_t n_rows, int32_t n_classes, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,
                           int64_t ld_out, void* stream);      /* autograd of dgn_net.py:75-78 */
+
+/* ---- input stage of the nets with positional encodings: embedding sum + Linear on pos_enc in one pass (dgn_node_input.hip) ---------------
+ * Replaces h = embedding_h(h) + embedding_pos_enc(g.ndata['pos_enc']) of nets/molecules_graph_regression/dgn_net.py:60-62,
+ * nets/SBMs_node_classification/dgn_net.py:57-59 and nets/HIV_graph_classification/dgn_net.py:64-66 (with in_feat_dropout inactive
+ * between the two terms): the lookup(s), an nn.Linear(K, hidden) with K of 2 to 20 -- a library GEMM on a shape dgn_linear_supported
+ * refuses -- and an add forward; the embedding backward(s), two GEMM gradients and a bias reduction backward.  idx [N, C] int64 (row
+ * stride ld_idx >= C, unit column stride), 1 <= C <= DGN_MULTI_EMBEDDING_MAX_COLS; tables / g_tables: HOST arrays of C DEVICE pointers to
+ * dense fp32 [dims[c], F] tables (they travel in the kernel arguments), dims: HOST array; pe [N, K] fp32 (row stride ld_pe >= K, unit
+ * column stride, base 4-byte aligned: a column slice of eig), 1 <= K <= DGN_NODE_INPUT_MAX_K; w [F, K] dense (torch's layout), b [F] or
+ * NULL.  N < 2^31.  (sum(dims) + K + 1) * F floats -- the backward's partial block -- and (K + 1) * F + 64 * (K + C) floats -- the forward's
+ * residents -- must each fit the CU's 160 KB of LDS: dgn_node_input_supported says whether they do (callers take the composition
+ * otherwise).  An index outside [0, dims[c]) is CLAMPED into the table.
+ *     forward   out[n, f] = (((0 + T_0[i_0][f]) + T_1[i_1][f]) + ...) + fmaf(w[f, K-1], pe[n, K-1], ... fmaf(w[f, 0], pe[n, 0], b[f])):
+ *               the table terms in column order, the linear terms in increasing k from the bias on (0 without one), the two partial
+ *               results added last.  out [N, F] (row stride ld_out >= F); dense rows (ld_out == F) at a 16-byte aligned base are
+ *               written as flat 16-byte chunks whatever F is.  One launch; w (transposed) and b resident in LDS.
+ *     backward  g_tables[c][r, :] = sum_{n: idx[n, c] = r} g[n, :] (rows without a hit: 0), g_w[f, k] = sum_n g[n, f] pe[n, k],
+ *               g_b[f] = sum_n g[n, f] (g_b: NULL = not wanted) in ONE pass over g [N, F] (row stride ld_g); two launches: per-workgroup
+ *               partial blocks [sum(dims) + K + 1, F] in LDS over contiguous row ranges (every column's adds in row order), then the
+ *               blocks added in a fixed order.  No floating-point atomics: the same input gives the same bits.  There is no gradient
+ *               for pe: it is data.  ws: 4-byte aligned, dgn_node_input_backward_workspace_bytes bytes (0 for unsupported arguments).
+ * N == 0: DGN_OK with nothing launched in either direction; the backward then leaves the gradients as they were (the sum over no row is
+ * the caller's zero fill). */
+#define DGN_NODE_INPUT_MAX_K 40      /* data/SBMs.py:135 prepares "40 PEs" */
+int dgn_node_input_supported(int32_t n_cols, const int32_t* dims, int32_t k, int32_t F);      /* dgn_net.py:60-62 */
+int dgn_node_input_forward(int64_t n_rows, int32_t n_cols, int32_t k, int32_t F, const int64_t* idx, int64_t ld_idx, const float* const* tables,
+                           const int32_t* dims, const float* pe, int64_t ld_pe, const float* w, const float* b, float* out, int64_t ld_out,
+                           void* stream);      /* molecules dgn_net.py:60-62, SBMs dgn_net.py:57-59, HIV dgn_net.py:64-66 */
+size_t dgn_node_input_backward_workspace_bytes(int64_t n_rows, int32_t n_cols, const int32_t* dims, int32_t k, int32_t F);
+int dgn_node_input_backward(int64_t n_rows, int32_t n_cols, int32_t k, int32_t F, const int64_t* idx, int64_t ld_idx, const int32_t* dims,
+                            const float* pe, int64_t ld_pe, const float* g, int64_t ld_g, float* const* g_tables, float* g_w, float* g_b, void* ws,
+                            size_t ws_bytes, void* stream);      /* autograd of the same lines */
 
 #ifdef __cplusplus
 }
