@@ -4,25 +4,28 @@
 // floating-point atomics, fixed-order reductions (the same input gives the same bits), every launch parameter a function of the shapes.
 //
 //   embed_forward   one workgroup per kEmbRows rows: W (transposed), b and the rows' x in LDS, every output b + sum_k W[f, k] x[r, k] in
-//                   increasing k; dense output rows leave as flat 16-byte chunks whatever the width (65, 75: a chunk may span two rows)
+//                   increasing k; dense output rows leave as flat 16-byte chunks whatever the width (65, 75: net_io::write_rows)
 //   embed_partial   one workgroup per contiguous row range: thread (sub, f) walks the rows sub, sub + n_sub, ... of column f of g and keeps
 //                   dW[f, 0 .. K) and db[f]; the sub-sequences are joined in order, the [K + 1, F] block goes to the workgroup's slot
 //   embed_fold      the slots added in a fixed order (wg::slot_sum16), dW in torch's [F, K] layout and db written
 //   ce_stats        one workgroup per contiguous row range, one lane per row: loss term, valid and hit counts -> slot b
-//   ce_rows         every workgroup folds the slots (block 0 writes loss and hits), then writes the gradient rows of its range
-//   (dgn::scale_rows_async, shared with the other losses: the autograd backward, g_saved * *g_loss)
+//   ce_rows         every workgroup folds the slots (net_io::fold_mean_slots; block 0 writes loss and hits), then writes the gradient rows
+//                   of its range
+//   (net_io::loss_backward: the autograd backward, g_saved * *g_loss)
 //
 // Both families are instantiated per width (K = 1 .. 8; the class count rounded up to a power of two, CP = 2 .. 64) so that a row lives
-// in registers under compile-time indices.
+// in registers under compile-time indices (net_io::load_scores, row_max, sum_exp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
-#include "dgn_common.hpp"
+#include "dgn_net_io.hpp"
 #include "dgn_wgrad.hpp"
 
 namespace dgn {
 namespace gcls {
+
+using namespace net_io;
 
 // ---- feature embedding ---------------------------------------------------------------------------------------------------------------
 
@@ -75,30 +78,7 @@ __global__ __launch_bounds__(kEmbThreads) void embed_forward(int64_t R, int F, c
         for (int k = 0; k < K; ++k) a = fmaf(s_w[k][f], s_x[r][k], a);
         return a;
     };
-    const int total = n * F;
-    if (flat) {                                 // ld_y == F, y 16-byte aligned: r0 F floats in front of this workgroup, a multiple of four
-        float* yb = y + r0 * F;
-        const int chunks = total >> 2;
-        for (int q = tid; q < chunks; q += kEmbThreads) {
-            int r = (4 * q) / F, f = 4 * q - r * F;
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = dot(r, f);
-                if (++f == F) { f = 0; ++r; }
-            }
-            stv<4>(yb + 4 * q, v);
-        }
-        for (int i = (chunks << 2) + tid; i < total; i += kEmbThreads) {      // (n F) mod 4 floats: the last workgroup's only
-            const int r = i / F;
-            yb[i] = dot(r, i - r * F);
-        }
-    } else {
-        for (int i = tid; i < total; i += kEmbThreads) {
-            const int r = i / F, f = i - r * F;
-            y[(r0 + r) * ld_y + f] = dot(r, f);
-        }
-    }
+    write_rows<kEmbThreads>(y, ld_y, r0, n, F, flat, dot);
 }
 
 template <int K>
@@ -160,44 +140,11 @@ __global__ __launch_bounds__(kFoldThreads) void embed_fold(int K, int F, int slo
 // ---- class cross-entropy with hit count ----------------------------------------------------------------------------------------------
 
 constexpr int kMaxC = DGN_CLASS_CE_MAX_CLASSES;
-constexpr int kCeThreads = 256;
-constexpr int kCeWaves = kCeThreads / kWave;
-constexpr int kCeMaxGroups = 256;
+constexpr int kCeThreads = kMeanThreads;
+constexpr int kCeWaves = kMeanWaves;
 constexpr int kCeMinRows = 256;                 // rows per workgroup at least: one per lane
 
-struct CeLayout {
-    int groups;
-    int64_t per;                                // rows per workgroup
-    size_t lossp, cnt, hit, bytes;
-};
-inline CeLayout ce_layout(int64_t n_rows) {
-    CeLayout L{};
-    const SlotSplit s = slot_split(n_rows, kCeMinRows, kCeMaxGroups);
-    L.groups = s.groups < 1 ? 1 : s.groups;
-    L.per = s.per;
-    L.lossp = 0;                                                // double [kCeMaxGroups]
-    L.cnt = L.lossp + kCeMaxGroups * sizeof(double);            // int64  [kCeMaxGroups]
-    L.hit = L.cnt + kCeMaxGroups * sizeof(int64_t);             // int64  [kCeMaxGroups]
-    L.bytes = L.hit + kCeMaxGroups * sizeof(int64_t);
-    return L;
-}
-
-// row's C scores into x[0 .. CP), -inf behind the C-th (exp(-inf - m) = 0: the row loops need no guard)
-template <int CP>
-__device__ __forceinline__ void load_scores(float (&x)[CP], const float* __restrict__ p, int C) {
-#pragma unroll
-    for (int c = 0; c < CP; ++c) x[c] = c < C ? p[c] : -INFINITY;
-}
-// the row's maximum (a NaN is skipped here and comes back through the sum) and sum_c exp(x[c] - m)
-template <int CP>
-__device__ __forceinline__ void max_and_sum(const float (&x)[CP], float& m, float& s) {
-    m = x[0];
-#pragma unroll
-    for (int c = 1; c < CP; ++c) m = fmaxf(m, x[c]);
-    s = 0.f;
-#pragma unroll
-    for (int c = 0; c < CP; ++c) s += expf(x[c] - m);
-}
+inline MeanLayout ce_layout(int64_t n_rows) { return mean_layout(n_rows, kCeMinRows, true); }
 
 template <int CP>
 __global__ __launch_bounds__(kCeThreads) void ce_stats(int64_t G, int C, const float* __restrict__ scores, int64_t ld,
@@ -216,8 +163,7 @@ __global__ __launch_bounds__(kCeThreads) void ce_stats(int64_t G, int C, const f
         float x[CP];
         load_scores<CP>(x, scores + n * ld, C);                  // (issued with the label's load, not behind it)
         if (y < 0) continue;                                     // a row that does not exist
-        float m, s;
-        max_and_sum<CP>(x, m, s);
+        const float m = row_max<CP>(x), s = sum_exp<CP>(x, m);
         float xy = NAN;                                          // a label >= C: the row's term is nan, nothing is read for it
         int best = 0;
         float bv = x[0];
@@ -242,20 +188,12 @@ __global__ __launch_bounds__(kCeThreads) void ce_rows(int64_t G, int C, const fl
                                                        const double* __restrict__ lossp, const int64_t* __restrict__ cnt,
                                                        const int64_t* __restrict__ hit, float* __restrict__ loss, int64_t* __restrict__ hits,
                                                        float* __restrict__ g, int64_t ld_g) {
-    __shared__ double s_red[kCeWaves];
-    __shared__ unsigned long long s_cnt, s_hit;
     const int tid = threadIdx.x, b = blockIdx.x;
-    if (tid == 0) { s_cnt = 0ull; s_hit = 0ull; }
-    __syncthreads();
-    if (tid < slots) {                                           // slots <= 256 = one per thread
-        if (cnt[tid] > 0) atomicAdd(&s_cnt, (unsigned long long)cnt[tid]);
-        if (hit[tid] > 0) atomicAdd(&s_hit, (unsigned long long)hit[tid]);
-    }
-    const double total = block_sum<kCeWaves>(tid < slots ? lossp[tid] : 0.0, s_red);
-    const int64_t V = (int64_t)s_cnt;
+    int64_t V, n_hit;
+    const double total = fold_mean_slots<true>(slots, lossp, cnt, hit, V, n_hit);
     if (b == 0 && tid == 0) {
         *loss = (float)(total / (double)V);                      // no valid row: 0 / 0 = nan, the mean over nothing
-        if (hits) *hits = (int64_t)s_hit;
+        if (hits) *hits = n_hit;
     }
     if (!g) return;
     const float vf = (float)V;
@@ -265,7 +203,7 @@ __global__ __launch_bounds__(kCeThreads) void ce_rows(int64_t G, int C, const fl
         float x[CP];
         load_scores<CP>(x, scores + n * ld, C);
         float m = 0.f, s = 1.f;
-        if (y >= 0) max_and_sum<CP>(x, m, s);
+        if (y >= 0) { m = row_max<CP>(x); s = sum_exp<CP>(x, m); }
         const float bad = y >= C ? NAN : 0.f;                    // a label >= C: a nan row, as its loss term
         float* gp = g + n * ld_g;
 #pragma unroll
@@ -304,7 +242,7 @@ extern "C" int dgn_feat_embed_forward(int64_t n_rows, int32_t k, int32_t f_out, 
         set_error("dgn_feat_embed_forward: 1 <= k <= %d and 1 <= f_out <= %d required (got %d, %d)", gcls::kMaxK, gcls::kMaxF, k, f_out);
         return DGN_ERR_INVALID;
     }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_feat_embed_forward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    if (!net_io::rows_in_range("dgn_feat_embed_forward", n_rows)) return DGN_ERR_INVALID;
     if (n_rows == 0) return DGN_OK;
     if (!x || !w || !y) { set_error("dgn_feat_embed_forward: null pointer"); return DGN_ERR_INVALID; }
     if (ld < k || ld_y < f_out) { set_error("dgn_feat_embed_forward: row stride below the row's width"); return DGN_ERR_INVALID; }
@@ -324,15 +262,12 @@ extern "C" int dgn_feat_embed_backward(int64_t n_rows, int32_t k, int32_t f_out,
         set_error("dgn_feat_embed_backward: 1 <= k <= %d and 1 <= f_out <= %d required (got %d, %d)", gcls::kMaxK, gcls::kMaxF, k, f_out);
         return DGN_ERR_INVALID;
     }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_feat_embed_backward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    if (!net_io::rows_in_range("dgn_feat_embed_backward", n_rows)) return DGN_ERR_INVALID;
     if (n_rows == 0) return DGN_OK;
     if (!x || !g || !g_w) { set_error("dgn_feat_embed_backward: null pointer"); return DGN_ERR_INVALID; }
     if (ld < k || ld_g < f_out) { set_error("dgn_feat_embed_backward: row stride below the row's width"); return DGN_ERR_INVALID; }
     const gcls::EmbLayout L = gcls::emb_layout(n_rows, k, f_out);
-    if (!ws || ws_bytes < L.bytes || (reinterpret_cast<uintptr_t>(ws) & 3)) {
-        set_error("dgn_feat_embed_backward: workspace of %zu bytes required, got %zu", L.bytes, ws_bytes);
-        return DGN_ERR_INVALID;
-    }
+    if (!net_io::workspace_ok("dgn_feat_embed_backward", ws, ws_bytes, L.bytes, 4)) return DGN_ERR_INVALID;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* part = static_cast<float*>(ws);
     const dim3 grid((unsigned)L.groups), block(gcls::kEmbThreads);
@@ -359,15 +294,12 @@ extern "C" int dgn_class_ce_forward(int64_t n_rows, int32_t n_classes, const flo
         set_error("dgn_class_ce_forward: 2 <= n_classes <= %d required (got %d)", gcls::kMaxC, C);
         return DGN_ERR_INVALID;
     }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_class_ce_forward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    if (!net_io::rows_in_range("dgn_class_ce_forward", n_rows)) return DGN_ERR_INVALID;
     if (!loss) { set_error("dgn_class_ce_forward: null loss"); return DGN_ERR_INVALID; }
     if (n_rows > 0 && (!scores || !labels)) { set_error("dgn_class_ce_forward: null scores / labels"); return DGN_ERR_INVALID; }
     if (ld < C || (g_scores && ld_g < C)) { set_error("dgn_class_ce_forward: row stride below n_classes"); return DGN_ERR_INVALID; }
-    const gcls::CeLayout L = gcls::ce_layout(n_rows);
-    if (!ws || ws_bytes < L.bytes || (reinterpret_cast<uintptr_t>(ws) & 7)) {
-        set_error("dgn_class_ce_forward: workspace of %zu bytes (8-byte aligned) required, got %zu", L.bytes, ws_bytes);
-        return DGN_ERR_INVALID;
-    }
+    const net_io::MeanLayout L = gcls::ce_layout(n_rows);
+    if (!net_io::workspace_ok("dgn_class_ce_forward", ws, ws_bytes, L.bytes, 8)) return DGN_ERR_INVALID;
     char* base = static_cast<char*>(ws);
     double* lossp = reinterpret_cast<double*>(base + L.lossp);
     int64_t* cnt = reinterpret_cast<int64_t*>(base + L.cnt);
@@ -381,11 +313,7 @@ extern "C" int dgn_class_ce_forward(int64_t n_rows, int32_t n_classes, const flo
         hipLaunchKernelGGL(gcls::ce_rows<CP>, g_scores ? grid : dim3(1), block, 0, st, n_rows, C, scores, ld, labels, L.per, L.groups,   \
                            (const double*)lossp, (const int64_t*)cnt, (const int64_t*)hit, loss, hits, g_scores, ld_g);                   \
     } while (0)
-    if (C <= 2) DGN_CLASS_CE_LAUNCH(2);
-    else if (C <= 4) DGN_CLASS_CE_LAUNCH(4);
-    else if (C <= 8) DGN_CLASS_CE_LAUNCH(8);
-    else if (C <= 16) DGN_CLASS_CE_LAUNCH(16);
-    else if (C <= 32) DGN_CLASS_CE_LAUNCH(32);
+    if (C <= 32) DGN_CLASS_POW2_DISPATCH(C, DGN_CLASS_CE_LAUNCH);
     else DGN_CLASS_CE_LAUNCH(64);
 #undef DGN_CLASS_CE_LAUNCH
     DGN_HIP_CHECK(hipGetLastError());
@@ -399,9 +327,5 @@ extern "C" int dgn_class_ce_backward(int64_t n_rows, int32_t n_classes, const fl
         set_error("dgn_class_ce_backward: 2 <= n_classes <= %d required (got %d)", gcls::kMaxC, C);
         return DGN_ERR_INVALID;
     }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_class_ce_backward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
-    if (n_rows == 0) return DGN_OK;
-    if (!g_saved || !g_loss || !g_scores) { set_error("dgn_class_ce_backward: null pointer"); return DGN_ERR_INVALID; }
-    if (ld_g < C || ld_out < C) { set_error("dgn_class_ce_backward: row stride below n_classes"); return DGN_ERR_INVALID; }
-    return scale_rows_async(n_rows, C, g_saved, ld_g, g_loss, g_scores, ld_out, static_cast<hipStream_t>(stream));
+    return net_io::loss_backward("dgn_class_ce_backward", "n_classes", n_rows, C, g_saved, ld_g, g_loss, g_scores, ld_out, stream);
 }

@@ -7,26 +7,29 @@
 //   emb_forward           one thread per (row, 1 / 2 / 4 consecutive features): h = ((0 + T_0[i_0]) + T_1[i_1]) + ... in column order --
 //                         the very adds of the torch composition, so the result is bit-equal to it
 //   emb_backward_partial  one workgroup per contiguous row range, all C tables as one partial table in LDS; thread (c, f) owns column f of
-//                         table c and walks the range's rows in order: a column's adds are sequential, no two threads share an address
+//                         table c and walks the range's rows in order (net_io::scatter_column): a column's adds are sequential, no two
+//                         threads share an address
 //   emb_backward_fold     one thread per table element: the workgroups' partials added in workgroup order (fp64), written to table c
 //   bce_stats             one workgroup per contiguous element range: labelled count (integer) and the fp64 sum of the loss terms
-//   bce_rows              every workgroup folds the slots (count, loss), block 0 writes the loss; then the gradient of its range
+//   bce_rows              every workgroup folds the slots (net_io::fold_mean_slots), block 0 writes the loss; then the gradient of its range
 //   (both instantiated twice: BceTerm, and L1Term for the masked L1 of the graph-regression net, nets/molecules_graph_regression/
 //    dgn_net.py:90-92 -- dgn_masked_mae_*)
-//   (dgn::scale_rows_async, shared with the node loss: the autograd backward, g_saved * *g_loss)
+//   (net_io::loss_backward: the autograd backward, g_saved * *g_loss)
 //
-// The tables' pointers travel in the kernel arguments (a struct by value): the parameters stay the separate nn.Embedding weights of the
-// state_dict and a captured graph holds their addresses like every other parameter's.  Indices outside a table are clamped (memory-safe).
+// The tables' pointers travel in the kernel arguments (net_io::Tables, a struct by value): the parameters stay the separate nn.Embedding
+// weights of the state_dict and a captured graph holds their addresses like every other parameter's.  Indices outside a table are clamped.
+// The table structs, the slot layout of the masked mean and the host-side checks are those of dgn_net_io.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
-#include "dgn_common.hpp"
+#include "dgn_net_io.hpp"
 
 namespace dgn {
 namespace mol_io {
 
-constexpr int kMaxCols = DGN_MULTI_EMBEDDING_MAX_COLS;
+using namespace net_io;
+
 constexpr int kLdsFloats = 160 * 1024 / 4;      // the partial tables of one workgroup: the CU's whole LDS (OGB atoms: 173 rows -> F <= 236)
 constexpr int kFwdThreads = 256;
 constexpr int kBwdThreads = 1024;               // C F columns to own (atoms at hidden 70: 630)
@@ -34,35 +37,12 @@ constexpr int kMaxGroups = 256;
 constexpr int kMinRows = 64;                    // rows per workgroup at least: few partial tables to fold for small batches
 constexpr int kFoldThreads = 256;
 
-struct Tables {
-    const float* t[kMaxCols];
-    int dims[kMaxCols];
-};
-struct GradTables {
-    float* t[kMaxCols];
-    int dims[kMaxCols];
-    int off[kMaxCols + 1];                      // first row of table c in the combined partial table
-};
-
 struct EmbLayout {
     int groups;
     int64_t per;                                // rows per workgroup
     int64_t total;                              // floats of the combined table
     size_t bytes;
 };
-
-inline int64_t table_rows(int32_t n_cols, const int32_t* dims) {
-    int64_t rows = 0;
-    for (int c = 0; c < n_cols; ++c) rows += dims[c];
-    return rows;
-}
-
-inline bool emb_args_ok(int32_t n_cols, const int32_t* dims, int32_t F) {
-    if (n_cols < 1 || n_cols > kMaxCols || !dims || F < 1) return false;
-    for (int c = 0; c < n_cols; ++c)
-        if (dims[c] < 1) return false;
-    return true;
-}
 
 inline EmbLayout emb_layout(int64_t n_rows, int64_t total) {
     EmbLayout L{};
@@ -73,8 +53,6 @@ inline EmbLayout emb_layout(int64_t n_rows, int64_t total) {
     L.bytes = (size_t)s.bound * (size_t)total * sizeof(float);       // sized by the upper bound of `groups`
     return L;
 }
-
-__device__ __forceinline__ int clamp_row(int64_t r, int dim) { return r < 0 ? 0 : (r >= dim ? dim - 1 : (int)r); }
 
 template <int VEC>
 __global__ __launch_bounds__(kFwdThreads) void emb_forward(int64_t N, int C, int F, const int64_t* __restrict__ idx, int64_t ld_idx, Tables tb,
@@ -110,26 +88,7 @@ __global__ __launch_bounds__(kBwdThreads) void emb_backward_partial(int64_t N, i
     const int items = C * F;
     for (int it = tid; it < items; it += kBwdThreads) {
         const int c = it / F, f = it - c * F;
-        const int dim = m.dims[c];
-        float* tab = s_tab + m.off[c] * F + f;
-        const int64_t* ip = idx + c;
-        const float* gp = g + f;
-        int64_t n = r0;
-        for (; n + 4 <= r1; n += 4) {            // four rows' loads in flight, their adds in row order
-            int64_t a[4];
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { a[k] = ip[(n + k) * ld_idx]; v[k] = gp[(n + k) * ld_g]; }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float* p = tab + clamp_row(a[k], dim) * F;
-                *p = *p + v[k];
-            }
-        }
-        for (; n < r1; ++n) {
-            float* p = tab + clamp_row(ip[n * ld_idx], dim) * F;
-            *p = *p + gp[n * ld_g];
-        }
+        scatter_column(s_tab + m.off[c] * F + f, m.dims[c], F, idx + c, ld_idx, g + f, ld_g, r0, r1);
     }
     __syncthreads();
     float* dst = part + (int64_t)b * total;
@@ -143,34 +102,17 @@ __global__ __launch_bounds__(kFoldThreads) void emb_backward_fold(int C, int F, 
 #pragma unroll 8
     for (int gidx = 0; gidx < G; ++gidx) s += (double)part[(int64_t)gidx * total + i];
     const int row = i / F, f = i - row * F;
-    int c = 0;
-    while (c + 1 < C && row >= m.off[c + 1]) ++c;
+    const int c = table_of_row(m, C, row);
     m.t[c][(int64_t)(row - m.off[c]) * F + f] = (float)s;
 }
 
 // ---- masked binary cross-entropy with logits ----------------------------------------------------------------------------------------
 
-constexpr int kBceThreads = 256;
-constexpr int kBceWaves = kBceThreads / kWave;
-constexpr int kBceMaxGroups = 256;
+constexpr int kBceThreads = kMeanThreads;
+constexpr int kBceWaves = kMeanWaves;
 constexpr int kBceMinElems = 2048;              // elements per workgroup at least
 
-struct BceLayout {
-    int groups;
-    int64_t per;                                // elements per workgroup
-    size_t lossp, cnt, bytes;
-};
-
-inline BceLayout bce_layout(int64_t n) {
-    BceLayout L{};
-    const SlotSplit s = slot_split(n, kBceMinElems, kBceMaxGroups);
-    L.groups = s.groups < 1 ? 1 : s.groups;
-    L.per = s.per;
-    L.lossp = 0;                                                // double [kBceMaxGroups]
-    L.cnt = L.lossp + kBceMaxGroups * sizeof(double);           // int64  [kBceMaxGroups]
-    L.bytes = L.cnt + kBceMaxGroups * sizeof(int64_t);
-    return L;
-}
+inline MeanLayout bce_layout(int64_t n) { return mean_layout(n, kBceMinElems, false); }
 
 // The per-entry term of a masked mean loss and its gradient (x: score, y: target, not NaN).  nf = (float)count and inv = (float)(1 / count)
 // are both at hand: each term keeps the arithmetic of the loss it replaces.
@@ -221,14 +163,9 @@ __global__ __launch_bounds__(kBceThreads) void bce_rows(int64_t n, int T, const 
                                                          int64_t ld_y, int64_t per, int G, const double* __restrict__ lossp,
                                                          const int64_t* __restrict__ cnt, float* __restrict__ loss, float* __restrict__ g,
                                                          int64_t ld_g) {
-    __shared__ double s_red[kBceWaves];
-    __shared__ unsigned long long s_cnt;
     const int tid = threadIdx.x, b = blockIdx.x;
-    if (tid == 0) s_cnt = 0ull;
-    __syncthreads();
-    if (tid < G && cnt[tid] > 0) atomicAdd(&s_cnt, (unsigned long long)cnt[tid]);      // G <= 256 = one slot per thread
-    const double total = block_sum<kBceWaves>(tid < G ? lossp[tid] : 0.0, s_red);
-    const int64_t labelled = (int64_t)s_cnt;
+    int64_t labelled, unused;
+    const double total = fold_mean_slots<false>(G, lossp, cnt, nullptr, labelled, unused);
     // no labelled entry: 0 / 0 = nan, the mean over an empty selection (train_PCBA_graph_classification.py:32-33)
     if (b == 0 && tid == 0) *loss = (float)(total / (double)labelled);
     if (!g) return;
@@ -250,33 +187,29 @@ __global__ __launch_bounds__(kBceThreads) void bce_rows(int64_t n, int T, const 
 using namespace dgn;
 
 extern "C" int dgn_multi_embedding_supported(int32_t n_cols, const int32_t* dims, int32_t F) {
-    if (!mol_io::emb_args_ok(n_cols, dims, F)) return 0;
-    return mol_io::table_rows(n_cols, dims) * (int64_t)F <= mol_io::kLdsFloats ? 1 : 0;
+    if (!net_io::tables_ok(n_cols, dims, F)) return 0;
+    return net_io::table_rows(n_cols, dims) * (int64_t)F <= mol_io::kLdsFloats ? 1 : 0;
 }
 
 extern "C" size_t dgn_multi_embedding_backward_workspace_bytes(int64_t n_rows, int32_t n_cols, const int32_t* dims, int32_t F) {
     if (n_rows < 0 || n_rows > INT32_MAX || !dgn_multi_embedding_supported(n_cols, dims, F)) return 0;
-    return mol_io::emb_layout(n_rows, mol_io::table_rows(n_cols, dims) * F).bytes;
+    return mol_io::emb_layout(n_rows, net_io::table_rows(n_cols, dims) * F).bytes;
 }
 
 extern "C" int dgn_multi_embedding_forward(int64_t n_rows, int32_t n_cols, int32_t F, const int64_t* idx, int64_t ld_idx, const float* const* tables,
                                            const int32_t* dims, float* out, int64_t ld_out, void* stream) {
-    if (!mol_io::emb_args_ok(n_cols, dims, F)) {
-        set_error("dgn_multi_embedding_forward: 1 <= n_cols <= %d tables of at least one row and F >= 1 required", mol_io::kMaxCols);
+    if (!net_io::tables_ok(n_cols, dims, F)) {
+        set_error("dgn_multi_embedding_forward: 1 <= n_cols <= %d tables of at least one row and F >= 1 required", net_io::kMaxCols);
         return DGN_ERR_INVALID;
     }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_multi_embedding_forward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    if (!net_io::rows_in_range("dgn_multi_embedding_forward", n_rows)) return DGN_ERR_INVALID;
     if (n_rows == 0) return DGN_OK;
     if (!idx || !tables || !out) { set_error("dgn_multi_embedding_forward: null pointer"); return DGN_ERR_INVALID; }
     if (ld_idx < n_cols || ld_out < F) { set_error("dgn_multi_embedding_forward: row stride below the row's width"); return DGN_ERR_INVALID; }
-    mol_io::Tables tb{};
+    net_io::Tables tb{};
+    if (!net_io::fill_tables("dgn_multi_embedding_forward", "table", n_cols, dims, tables, tb)) return DGN_ERR_INVALID;
     uintptr_t align = reinterpret_cast<uintptr_t>(out) | (uintptr_t)(ld_out * sizeof(float)) | (uintptr_t)((int64_t)F * sizeof(float));
-    for (int c = 0; c < n_cols; ++c) {
-        if (!tables[c]) { set_error("dgn_multi_embedding_forward: null table %d", c); return DGN_ERR_INVALID; }
-        tb.t[c] = tables[c];
-        tb.dims[c] = dims[c];
-        align |= reinterpret_cast<uintptr_t>(tables[c]);
-    }
+    for (int c = 0; c < n_cols; ++c) align |= reinterpret_cast<uintptr_t>(tables[c]);
     const int vec = (align & 15) == 0 ? 4 : ((align & 7) == 0 ? 2 : 1);     // 16-byte pieces where the rows allow them
     const int64_t blocks = (n_rows * (F / vec) + mol_io::kFwdThreads - 1) / mol_io::kFwdThreads;
     if (blocks > INT32_MAX) { set_error("dgn_multi_embedding_forward: n_rows x F beyond the grid range"); return DGN_ERR_INVALID; }
@@ -291,32 +224,24 @@ extern "C" int dgn_multi_embedding_forward(int64_t n_rows, int32_t n_cols, int32
 
 extern "C" int dgn_multi_embedding_backward(int64_t n_rows, int32_t n_cols, int32_t F, const int64_t* idx, int64_t ld_idx, const int32_t* dims,
                                             const float* g, int64_t ld_g, float* const* g_tables, void* ws, size_t ws_bytes, void* stream) {
-    if (!mol_io::emb_args_ok(n_cols, dims, F)) {
-        set_error("dgn_multi_embedding_backward: 1 <= n_cols <= %d tables of at least one row and F >= 1 required", mol_io::kMaxCols);
+    if (!net_io::tables_ok(n_cols, dims, F)) {
+        set_error("dgn_multi_embedding_backward: 1 <= n_cols <= %d tables of at least one row and F >= 1 required", net_io::kMaxCols);
         return DGN_ERR_INVALID;
     }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_multi_embedding_backward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
-    const int64_t total = mol_io::table_rows(n_cols, dims) * F;
+    if (!net_io::rows_in_range("dgn_multi_embedding_backward", n_rows)) return DGN_ERR_INVALID;
+    const int64_t total = net_io::table_rows(n_cols, dims) * F;
     if (total > mol_io::kLdsFloats) {
         set_error("dgn_multi_embedding_backward: %lld table floats exceed the LDS budget of %d (dgn_multi_embedding_supported)", (long long)total,
                   mol_io::kLdsFloats);
         return DGN_ERR_INVALID;
     }
     if (!g_tables) { set_error("dgn_multi_embedding_backward: null pointer"); return DGN_ERR_INVALID; }
-    mol_io::GradTables m{};
-    for (int c = 0; c < n_cols; ++c) {
-        if (!g_tables[c]) { set_error("dgn_multi_embedding_backward: null gradient table %d", c); return DGN_ERR_INVALID; }
-        m.t[c] = g_tables[c];
-        m.dims[c] = dims[c];
-        m.off[c + 1] = m.off[c] + dims[c];
-    }
+    net_io::GradTables m{};
+    if (!net_io::fill_tables("dgn_multi_embedding_backward", "gradient table", n_cols, dims, g_tables, m)) return DGN_ERR_INVALID;
     if (n_rows > 0 && (!idx || !g)) { set_error("dgn_multi_embedding_backward: null pointer"); return DGN_ERR_INVALID; }
     if (n_rows > 0 && (ld_idx < n_cols || ld_g < F)) { set_error("dgn_multi_embedding_backward: row stride below the row's width"); return DGN_ERR_INVALID; }
     const mol_io::EmbLayout L = mol_io::emb_layout(n_rows, total);
-    if (!ws || ws_bytes < L.bytes || (reinterpret_cast<uintptr_t>(ws) & 3)) {
-        set_error("dgn_multi_embedding_backward: workspace of %zu bytes required, got %zu", L.bytes, ws_bytes);
-        return DGN_ERR_INVALID;
-    }
+    if (!net_io::workspace_ok("dgn_multi_embedding_backward", ws, ws_bytes, L.bytes, 4)) return DGN_ERR_INVALID;
     hipStream_t st = static_cast<hipStream_t>(stream);
     static LdsOptIn lds_ok{0};
     DGN_HIP_CHECK(allow_lds(lds_ok, mol_io::kLdsFloats * (int)sizeof(float), &mol_io::emb_backward_partial));
@@ -341,17 +266,14 @@ static int masked_mean_forward(const char* who, int64_t n_rows, int32_t n_tasks,
                                float* loss, float* g_scores, int64_t ld_g, void* ws, size_t ws_bytes, void* stream) {
     const int T = n_tasks;
     if (T < 1) { set_error("%s: n_tasks >= 1 required (got %d)", who, T); return DGN_ERR_INVALID; }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("%s: n_rows beyond the int32 range", who); return DGN_ERR_INVALID; }
+    if (!net_io::rows_in_range(who, n_rows)) return DGN_ERR_INVALID;
     if (!loss) { set_error("%s: null loss", who); return DGN_ERR_INVALID; }
     if (n_rows > 0 && (!scores || !labels)) { set_error("%s: null scores / labels", who); return DGN_ERR_INVALID; }
     if (ld < T || ld_y < T || (g_scores && ld_g < T)) { set_error("%s: row stride below n_tasks", who); return DGN_ERR_INVALID; }
     const int64_t n = n_rows * T;
     if (n > (int64_t)INT32_MAX * 64) { set_error("%s: n_rows x n_tasks beyond the grid range", who); return DGN_ERR_INVALID; }
-    const mol_io::BceLayout L = mol_io::bce_layout(n);
-    if (!ws || ws_bytes < L.bytes || (reinterpret_cast<uintptr_t>(ws) & 7)) {
-        set_error("%s: workspace of %zu bytes (8-byte aligned) required, got %zu", who, L.bytes, ws_bytes);
-        return DGN_ERR_INVALID;
-    }
+    const net_io::MeanLayout L = mol_io::bce_layout(n);
+    if (!net_io::workspace_ok(who, ws, ws_bytes, L.bytes, 8)) return DGN_ERR_INVALID;
     char* base = static_cast<char*>(ws);
     double* lossp = reinterpret_cast<double*>(base + L.lossp);
     int64_t* cnt = reinterpret_cast<int64_t*>(base + L.cnt);
@@ -375,12 +297,7 @@ static int masked_mean_backward(const char* who, int64_t n_rows, int32_t n_tasks
                                 float* g_scores, int64_t ld_out, void* stream) {
     const int T = n_tasks;
     if (T < 1) { set_error("%s: n_tasks >= 1 required (got %d)", who, T); return DGN_ERR_INVALID; }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("%s: n_rows beyond the int32 range", who); return DGN_ERR_INVALID; }
-    if (n_rows == 0) return DGN_OK;
-    if (!g_saved || !g_loss || !g_scores) { set_error("%s: null pointer", who); return DGN_ERR_INVALID; }
-    if (ld_g < T || ld_out < T) { set_error("%s: row stride below n_tasks", who); return DGN_ERR_INVALID; }
-    if (n_rows * T > (int64_t)INT32_MAX * 64) { set_error("%s: n_rows x n_tasks beyond the grid range", who); return DGN_ERR_INVALID; }
-    return scale_rows_async(n_rows, T, g_saved, ld_g, g_loss, g_scores, ld_out, static_cast<hipStream_t>(stream));
+    return net_io::loss_backward(who, "n_tasks", n_rows, T, g_saved, ld_g, g_loss, g_scores, ld_out, stream);
 }
 
 extern "C" int dgn_masked_bce_backward(int64_t n_rows, int32_t n_tasks, const float* g_saved, int64_t ld_g, const float* g_loss, float* g_scores,

@@ -17,10 +17,12 @@
 
 #include <cmath>
 
-#include "dgn_common.hpp"
+#include "dgn_net_io.hpp"
 
 namespace dgn {
 namespace node_ce {
+
+using namespace net_io;      // load_scores, row_max: the score-row helpers shared with the class cross-entropy
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
@@ -63,7 +65,7 @@ __device__ __forceinline__ float class_weight(int64_t V, int64_t count) {
     return count > 0 ? (float)(V - count) / (float)V : 0.f;
 }
 
-// row n's C scores into x[0 .. CP), -inf behind the C-th (exp(-inf - m) = 0: the row loops need no guard)
+// row n's C scores into x[0 .. CP): net_io::load_scores, or as 8- / 16-byte pieces
 template <int CP>
 __device__ __forceinline__ void load_row(float (&x)[CP], const float* __restrict__ p, int C, bool vec) {
     if (vec) {                              // C == CP, dense rows, 16-byte (CP = 2: 8-byte) aligned
@@ -78,8 +80,7 @@ __device__ __forceinline__ void load_row(float (&x)[CP], const float* __restrict
             }
         }
     } else {
-#pragma unroll
-        for (int c = 0; c < CP; ++c) x[c] = c < C ? p[c] : -INFINITY;
+        load_scores<CP>(x, p, C);
     }
 }
 template <int CP>
@@ -241,10 +242,8 @@ __global__ __launch_bounds__(kThreads) void node_ce_rows(int64_t N, int C, const
             continue;
         }
         const int y = (int)y64;
-        float m = x[0];
-#pragma unroll
-        for (int c = 1; c < CP; ++c) m = fmaxf(m, x[c]);
-        float e[CP], s = 0.f, xy = 0.f;
+        const float m = row_max<CP>(x);
+        float e[CP], s = 0.f, xy = 0.f;                                 // (sum exp as net_io::sum_exp adds it, the terms kept for the gradient)
 #pragma unroll
         for (int c = 0; c < CP; ++c) {
             e[c] = expf(x[c] - m);
@@ -319,7 +318,7 @@ extern "C" int dgn_node_ce_forward(int64_t n_rows, int32_t n_classes, const floa
                                    void* stream) {
     const int C = n_classes;
     if (C < 1 || C > node_ce::kMaxC) { set_error("dgn_node_ce_forward: 1 <= n_classes <= 32 required (got %d)", C); return DGN_ERR_INVALID; }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_node_ce_forward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    if (!net_io::rows_in_range("dgn_node_ce_forward", n_rows)) return DGN_ERR_INVALID;
     if (!loss) { set_error("dgn_node_ce_forward: null loss"); return DGN_ERR_INVALID; }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_rows == 0) {
@@ -331,10 +330,7 @@ extern "C" int dgn_node_ce_forward(int64_t n_rows, int32_t n_classes, const floa
     if (!scores || !labels) { set_error("dgn_node_ce_forward: null scores / labels"); return DGN_ERR_INVALID; }
     if (ld < C || (g_scores && ld_g < C)) { set_error("dgn_node_ce_forward: row stride below n_classes"); return DGN_ERR_INVALID; }
     const node_ce::Layout L = node_ce::layout(n_rows, C);
-    if (!ws || ws_bytes < L.bytes || (reinterpret_cast<uintptr_t>(ws) & 7)) {
-        set_error("dgn_node_ce_forward: workspace of %zu bytes (8-byte aligned) required, got %zu", L.bytes, ws_bytes);
-        return DGN_ERR_INVALID;
-    }
+    if (!net_io::workspace_ok("dgn_node_ce_forward", ws, ws_bytes, L.bytes, 8)) return DGN_ERR_INVALID;
     char* base = static_cast<char*>(ws);
     double* cols = reinterpret_cast<double*>(base + L.cols);
     double* lossp = reinterpret_cast<double*>(base + L.lossp);
@@ -349,11 +345,7 @@ extern "C" int dgn_node_ce_forward(int64_t n_rows, int32_t n_classes, const floa
         hipLaunchKernelGGL(node_ce::node_ce_rows<CP>, grid, block, 0, st, n_rows, C, scores, ld, labels, L.per, L.groups, (const int*)cnt,  \
                            (const float*)colm, (const double*)cols, g_scores, ld_g, lossp, cmp);                                            \
     } while (0)
-    if (C <= 2) DGN_NODE_CE_LAUNCH(2);
-    else if (C <= 4) DGN_NODE_CE_LAUNCH(4);
-    else if (C <= 8) DGN_NODE_CE_LAUNCH(8);
-    else if (C <= 16) DGN_NODE_CE_LAUNCH(16);
-    else DGN_NODE_CE_LAUNCH(32);
+    DGN_CLASS_POW2_DISPATCH(C, DGN_NODE_CE_LAUNCH);
 #undef DGN_NODE_CE_LAUNCH
     hipLaunchKernelGGL(node_ce::node_ce_finish, dim3(1), block, 0, st, C, L.groups, (const int*)cnt, (const double*)lossp, (const int*)cmp, loss,
                        weight, confusion);
@@ -365,9 +357,5 @@ extern "C" int dgn_node_ce_backward(int64_t n_rows, int32_t n_classes, const flo
                                     float* g_scores, int64_t ld_out, void* stream) {
     const int C = n_classes;
     if (C < 1 || C > node_ce::kMaxC) { set_error("dgn_node_ce_backward: 1 <= n_classes <= 32 required (got %d)", C); return DGN_ERR_INVALID; }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_node_ce_backward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
-    if (n_rows == 0) return DGN_OK;
-    if (!g_saved || !g_loss || !g_scores) { set_error("dgn_node_ce_backward: null pointer"); return DGN_ERR_INVALID; }
-    if (ld_g < C || ld_out < C) { set_error("dgn_node_ce_backward: row stride below n_classes"); return DGN_ERR_INVALID; }
-    return scale_rows_async(n_rows, C, g_saved, ld_g, g_loss, g_scores, ld_out, static_cast<hipStream_t>(stream));
+    return net_io::loss_backward("dgn_node_ce_backward", "n_classes", n_rows, C, g_saved, ld_g, g_loss, g_scores, ld_out, stream);
 }

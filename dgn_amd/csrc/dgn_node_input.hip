@@ -7,26 +7,27 @@
 //
 //   forward           one workgroup per kFwdRows rows: W (transposed), b, the rows' pe and their clamped table rows in LDS; an output is
 //                     (((0 + T_0[i_0]) + T_1[i_1]) + ...) + fmaf(W[f, K-1], pe[K-1], ... fmaf(W[f, 0], pe[0], b[f])): the table terms in
-//                     column order (mol_io::emb_forward), the linear terms in increasing k from the bias on (gcls::embed_forward), the two
-//                     partial results added last.  Dense output rows leave as flat 16-byte chunks whatever F is (a chunk may span two rows).
-//   backward_partial  one workgroup per contiguous row range, one combined [sum(dims) + K + 1, F] block in LDS: the table rows as
-//                     mol_io::emb_backward_partial lays them out, then K rows dW[:, k] and one row db as gcls::embed_partial does.  Thread
-//                     (q, f) owns column f of table q, of dW[:, k] or of db and walks the range's rows in order: a column's adds are
-//                     sequential and no two threads share an address
+//                     column order, the linear terms in increasing k from the bias on, the two partial results added last.  Dense output
+//                     rows leave as flat 16-byte chunks whatever F is (net_io::write_rows).
+//   backward_partial  one workgroup per contiguous row range, one combined [sum(dims) + K + 1, F] block in LDS: the table rows at
+//                     GradTables::off, then K rows dW[:, k] and one row db.  Thread (q, f) owns column f of table q
+//                     (net_io::scatter_column), of dW[:, k] or of db and walks the range's rows in order: a column's adds are sequential
+//                     and no two threads share an address
 //   backward_fold     the workgroups' blocks added in a fixed order (wg::slot_sum16), the table rows written to the separate tables, dW in
 //                     torch's [F, K] layout, db
 //
-// The tables' pointers travel in the kernel arguments (a struct by value), as in dgn_mol_io.hip.  Indices outside a table are clamped.
+// The tables' pointers travel in the kernel arguments (net_io::Tables, a struct by value).  Indices outside a table are clamped.
 // pe is read with 4-byte loads only: the nets pass eig[:, 1:K+1], a column slice whose base is 4-byte aligned and no more.
 #include <hip/hip_runtime.h>
 
-#include "dgn_common.hpp"
+#include "dgn_net_io.hpp"
 #include "dgn_wgrad.hpp"
 
 namespace dgn {
 namespace node_input {
 
-constexpr int kMaxCols = DGN_MULTI_EMBEDDING_MAX_COLS;
+using namespace net_io;
+
 constexpr int kMaxK = DGN_NODE_INPUT_MAX_K;
 constexpr int kLdsFloats = 160 * 1024 / 4;      // the combined partial block of one workgroup: the CU's whole LDS
 constexpr int kFwdThreads = 256;
@@ -38,14 +39,8 @@ constexpr int kFoldThreads = wg::kSumWaves * kWave;
 
 static_assert(kFwdRows % 4 == 0, "forward's flat chunks");
 
-struct Tables {
-    const float* t[kMaxCols];
-    int dims[kMaxCols];
-};
 struct Grads {
-    float* t[kMaxCols];
-    int dims[kMaxCols];
-    int off[kMaxCols + 1];                      // first row of table c in the combined block; off[C] = first row of dW
+    GradTables tab;                             // tab.off[C] = first row of dW in the combined block
     float* dw;                                  // [F, K]
     float* db;                                  // [F] or NULL
 };
@@ -57,18 +52,7 @@ struct Layout {
     size_t bytes;
 };
 
-inline int64_t table_rows(int32_t n_cols, const int32_t* dims) {
-    int64_t rows = 0;
-    for (int c = 0; c < n_cols; ++c) rows += dims[c];
-    return rows;
-}
-
-inline bool args_ok(int32_t n_cols, const int32_t* dims, int32_t K, int32_t F) {
-    if (n_cols < 1 || n_cols > kMaxCols || !dims || K < 1 || K > kMaxK || F < 1) return false;
-    for (int c = 0; c < n_cols; ++c)
-        if (dims[c] < 1) return false;
-    return true;
-}
+inline bool args_ok(int32_t n_cols, const int32_t* dims, int32_t K, int32_t F) { return tables_ok(n_cols, dims, F) && K >= 1 && K <= kMaxK; }
 
 inline int64_t block_floats(int32_t n_cols, const int32_t* dims, int32_t K, int32_t F) { return (table_rows(n_cols, dims) + K + 1) * (int64_t)F; }
 // forward: W^T [K, F], b [F], pe [kFwdRows, K], clamped rows [kFwdRows, C]
@@ -87,8 +71,6 @@ inline Layout layout(int64_t n_rows, int64_t total) {
     L.bytes = (size_t)s.bound * (size_t)total * sizeof(float);       // sized by the upper bound of `groups`
     return L;
 }
-
-__device__ __forceinline__ int clamp_row(int64_t r, int dim) { return r < 0 ? 0 : (r >= dim ? dim - 1 : (int)r); }
 
 __global__ __launch_bounds__(kFwdThreads) void node_input_forward(int64_t N, int C, int K, int F, const int64_t* __restrict__ idx, int64_t ld_idx,
                                                                    Tables tb, const float* __restrict__ pe, int64_t ld_pe,
@@ -116,30 +98,7 @@ __global__ __launch_bounds__(kFwdThreads) void node_input_forward(int64_t N, int
         for (int k = 0; k < K; ++k) a = fmaf(s_w[k * F + f], x[k], a);
         return t + a;
     };
-    const int total = n * F;
-    if (flat) {                                 // ld_out == F, out 16-byte aligned: r0 F floats in front of this workgroup, a multiple of four
-        float* ob = out + r0 * F;
-        const int chunks = total >> 2;
-        for (int q = tid; q < chunks; q += kFwdThreads) {
-            int r = (4 * q) / F, f = 4 * q - r * F;
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = value(r, f);
-                if (++f == F) { f = 0; ++r; }
-            }
-            stv<4>(ob + 4 * q, v);
-        }
-        for (int i = (chunks << 2) + tid; i < total; i += kFwdThreads) {      // (n F) mod 4 floats: the last workgroup's only
-            const int r = i / F;
-            ob[i] = value(r, i - r * F);
-        }
-    } else {
-        for (int i = tid; i < total; i += kFwdThreads) {
-            const int r = i / F, f = i - r * F;
-            out[(r0 + r) * ld_out + f] = value(r, f);
-        }
-    }
+    write_rows<kFwdThreads>(out, ld_out, r0, n, F, flat, value);
 }
 
 __global__ __launch_bounds__(kBwdThreads) void node_input_backward_partial(int64_t N, int C, int K, int F, const int64_t* __restrict__ idx,
@@ -148,7 +107,7 @@ __global__ __launch_bounds__(kBwdThreads) void node_input_backward_partial(int64
                                                                             float* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) float s_blk[];
     const int tid = threadIdx.x, b = blockIdx.x;
-    const int lin0 = m.off[C];                   // first row of dW[:, 0]
+    const int lin0 = m.tab.off[C];               // first row of dW[:, 0]
     const int total = (lin0 + K + 1) * F;
     for (int i = tid; i < total; i += kBwdThreads) s_blk[i] = 0.f;
     __syncthreads();
@@ -159,24 +118,7 @@ __global__ __launch_bounds__(kBwdThreads) void node_input_backward_partial(int64
         const float* gp = g + f;
         int64_t n = r0;
         if (q < C) {                             // column f of table q
-            const int dim = m.dims[q];
-            float* tab = s_blk + m.off[q] * F + f;
-            const int64_t* ip = idx + q;
-            for (; n + 4 <= r1; n += 4) {        // four rows' loads in flight, their adds in row order
-                int64_t a[4];
-                float v[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { a[k] = ip[(n + k) * ld_idx]; v[k] = gp[(n + k) * ld_g]; }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float* p = tab + clamp_row(a[k], dim) * F;
-                    *p = *p + v[k];
-                }
-            }
-            for (; n < r1; ++n) {
-                float* p = tab + clamp_row(ip[n * ld_idx], dim) * F;
-                *p = *p + gp[n * ld_g];
-            }
+            scatter_column(s_blk + m.tab.off[q] * F + f, m.tab.dims[q], F, idx + q, ld_idx, gp, ld_g, r0, r1);
         } else if (q < C + K) {                  // dW[f, k]
             const float* pp = pe + (q - C);
             float acc = 0.f;
@@ -214,11 +156,10 @@ __global__ __launch_bounds__(kFoldThreads) void node_input_backward_fold(int C, 
     const int i = blockIdx.x * 64 + (threadIdx.x & 63);
     const float v = wg::slot_sum16(part + i, total, slots, i < total, red);
     if (threadIdx.x < 64 && i < total) {
-        const int row = i / F, f = i - row * F, lin0 = m.off[C];
+        const int row = i / F, f = i - row * F, lin0 = m.tab.off[C];
         if (row < lin0) {
-            int c = 0;
-            while (c + 1 < C && row >= m.off[c + 1]) ++c;
-            m.t[c][(int64_t)(row - m.off[c]) * F + f] = v;
+            const int c = table_of_row(m.tab, C, row);
+            m.tab.t[c][(int64_t)(row - m.tab.off[c]) * F + f] = v;
         } else if (row < lin0 + K) {
             m.dw[(int64_t)f * K + (row - lin0)] = v;
         } else if (m.db) {
@@ -245,7 +186,7 @@ extern "C" int dgn_node_input_forward(int64_t n_rows, int32_t n_cols, int32_t k,
                                       const float* const* tables, const int32_t* dims, const float* pe, int64_t ld_pe, const float* w,
                                       const float* b, float* out, int64_t ld_out, void* stream) {
     if (!node_input::args_ok(n_cols, dims, k, F)) {
-        set_error("dgn_node_input_forward: 1 <= n_cols <= %d tables of at least one row, 1 <= k <= %d and F >= 1 required", node_input::kMaxCols,
+        set_error("dgn_node_input_forward: 1 <= n_cols <= %d tables of at least one row, 1 <= k <= %d and F >= 1 required", net_io::kMaxCols,
                   node_input::kMaxK);
         return DGN_ERR_INVALID;
     }
@@ -253,16 +194,12 @@ extern "C" int dgn_node_input_forward(int64_t n_rows, int32_t n_cols, int32_t k,
         set_error("dgn_node_input_forward: the shape exceeds the LDS budget of %d floats (dgn_node_input_supported)", node_input::kLdsFloats);
         return DGN_ERR_INVALID;
     }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_node_input_forward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    if (!net_io::rows_in_range("dgn_node_input_forward", n_rows)) return DGN_ERR_INVALID;
     if (n_rows == 0) return DGN_OK;
     if (!idx || !tables || !pe || !w || !out) { set_error("dgn_node_input_forward: null pointer"); return DGN_ERR_INVALID; }
     if (ld_idx < n_cols || ld_pe < k || ld_out < F) { set_error("dgn_node_input_forward: row stride below the row's width"); return DGN_ERR_INVALID; }
-    node_input::Tables tb{};
-    for (int c = 0; c < n_cols; ++c) {
-        if (!tables[c]) { set_error("dgn_node_input_forward: null table %d", c); return DGN_ERR_INVALID; }
-        tb.t[c] = tables[c];
-        tb.dims[c] = dims[c];
-    }
+    net_io::Tables tb{};
+    if (!net_io::fill_tables("dgn_node_input_forward", "table", n_cols, dims, tables, tb)) return DGN_ERR_INVALID;
     const int lds = (int)(node_input::forward_floats(n_cols, k, F) * sizeof(float));
     static LdsOptIn lds_ok{0};
     DGN_HIP_CHECK(allow_lds(lds_ok, node_input::kLdsFloats * (int)sizeof(float), &node_input::node_input_forward));
@@ -278,7 +215,7 @@ extern "C" int dgn_node_input_backward(int64_t n_rows, int32_t n_cols, int32_t k
                                        const int32_t* dims, const float* pe, int64_t ld_pe, const float* g, int64_t ld_g,
                                        float* const* g_tables, float* g_w, float* g_b, void* ws, size_t ws_bytes, void* stream) {
     if (!node_input::args_ok(n_cols, dims, k, F)) {
-        set_error("dgn_node_input_backward: 1 <= n_cols <= %d tables of at least one row, 1 <= k <= %d and F >= 1 required", node_input::kMaxCols,
+        set_error("dgn_node_input_backward: 1 <= n_cols <= %d tables of at least one row, 1 <= k <= %d and F >= 1 required", net_io::kMaxCols,
                   node_input::kMaxK);
         return DGN_ERR_INVALID;
     }
@@ -286,25 +223,17 @@ extern "C" int dgn_node_input_backward(int64_t n_rows, int32_t n_cols, int32_t k
         set_error("dgn_node_input_backward: the shape exceeds the LDS budget of %d floats (dgn_node_input_supported)", node_input::kLdsFloats);
         return DGN_ERR_INVALID;
     }
-    if (n_rows < 0 || n_rows > INT32_MAX) { set_error("dgn_node_input_backward: n_rows beyond the int32 range"); return DGN_ERR_INVALID; }
+    if (!net_io::rows_in_range("dgn_node_input_backward", n_rows)) return DGN_ERR_INVALID;
     if (n_rows == 0) return DGN_OK;
     if (!idx || !pe || !g || !g_tables || !g_w) { set_error("dgn_node_input_backward: null pointer"); return DGN_ERR_INVALID; }
     if (ld_idx < n_cols || ld_pe < k || ld_g < F) { set_error("dgn_node_input_backward: row stride below the row's width"); return DGN_ERR_INVALID; }
     node_input::Grads m{};
-    for (int c = 0; c < n_cols; ++c) {
-        if (!g_tables[c]) { set_error("dgn_node_input_backward: null gradient table %d", c); return DGN_ERR_INVALID; }
-        m.t[c] = g_tables[c];
-        m.dims[c] = dims[c];
-        m.off[c + 1] = m.off[c] + dims[c];
-    }
+    if (!net_io::fill_tables("dgn_node_input_backward", "gradient table", n_cols, dims, g_tables, m.tab)) return DGN_ERR_INVALID;
     m.dw = g_w;
     m.db = g_b;
     const int64_t total = node_input::block_floats(n_cols, dims, k, F);
     const node_input::Layout L = node_input::layout(n_rows, total);
-    if (!ws || ws_bytes < L.bytes || (reinterpret_cast<uintptr_t>(ws) & 3)) {
-        set_error("dgn_node_input_backward: workspace of %zu bytes required, got %zu", L.bytes, ws_bytes);
-        return DGN_ERR_INVALID;
-    }
+    if (!net_io::workspace_ok("dgn_node_input_backward", ws, ws_bytes, L.bytes, 4)) return DGN_ERR_INVALID;
     hipStream_t st = static_cast<hipStream_t>(stream);
     static LdsOptIn lds_ok{0};
     DGN_HIP_CHECK(allow_lds(lds_ok, node_input::kLdsFloats * (int)sizeof(float), &node_input::node_input_backward_partial));

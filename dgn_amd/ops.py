@@ -1845,9 +1845,31 @@ def assemble_operands(maps, params):
     return _AssembleOperands.apply(maps, *params)
 
 
+def _workspace(n_bytes: int, dtype: torch.dtype, dev) -> torch.Tensor:
+    """the scratch of a C call, ``n_bytes`` in elements of ``dtype`` (the alignment the call asks for); never an empty tensor"""
+    return torch.empty(max(n_bytes // dtype.itemsize, 1), dtype=dtype, device=dev)
+
+
+def _wants_grad(scores: torch.Tensor) -> bool:
+    """The gradient policy of the four losses, decided in the public function: inside Function.forward grad mode is always off and
+    ``ctx.needs_input_grad`` reports ``requires_grad`` whatever the grad mode.  Under ``torch.no_grad()``, or for scores that ask for
+    none, no gradient buffer is allocated or written."""
+    return torch.is_grad_enabled() and scores.requires_grad
+
+
+def _loss_backward(entry: str, g: torch.Tensor, g_loss: torch.Tensor) -> torch.Tensor:
+    """the backward of a loss that saved its gradient: ``g * g_loss`` through ``dgn_*_backward``, one launch"""
+    g_loss = g_loss.to(torch.float32).contiguous()
+    out = torch.empty_like(g)
+    rc = getattr(_lib.load(), entry)(g.shape[0], g.shape[1], g.data_ptr(), g.stride(0), g_loss.data_ptr(), out.data_ptr(), out.stride(0),
+                                     _lib.stream_ptr(g.device))
+    _lib.check(rc, entry)
+    return out
+
+
 class _BalancedCrossEntropy(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, scores, labels, n_classes, want_confusion):
+    def forward(ctx, scores, labels, n_classes, want_confusion, want_grad):
         lib = _lib.load()
         if not scores.is_cuda:
             raise _lib.DgnError("balanced_cross_entropy: CUDA tensors only (dgn_amd has no CPU path)")
@@ -1859,17 +1881,15 @@ class _BalancedCrossEntropy(torch.autograd.Function):
             scores = scores.contiguous()
         labels = labels.contiguous()
         N, dev = scores.shape[0], scores.device
-        want_grad = ctx.needs_input_grad[0]                   # (False under torch.no_grad(): no gradient buffer is written)
         out = torch.empty(1 + n_classes, dtype=torch.float32, device=dev)           # [loss | weight]
         g = torch.empty(N, n_classes, dtype=torch.float32, device=dev) if want_grad else None
         cm = torch.empty(n_classes, n_classes, dtype=torch.int64, device=dev) if want_confusion else None
         ws_bytes = lib.dgn_node_ce_workspace_bytes(N, n_classes)
-        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
-        rc = lib.dgn_node_ce_forward(N, n_classes, scores.data_ptr(), scores.stride(0) if N > 1 else n_classes, labels.data_ptr(), out.data_ptr(),
-                                     out.data_ptr() + 4, _ptr(g), n_classes, _ptr(cm), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        ws = _workspace(ws_bytes, torch.float64, dev)
+        rc = lib.dgn_node_ce_forward(N, n_classes, scores.data_ptr(), _ld(scores), labels.data_ptr(), out.data_ptr(), out.data_ptr() + 4,
+                                     _ptr(g), n_classes, _ptr(cm), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
         _lib.check(rc, "dgn_node_ce_forward")
         ctx.save_for_backward(g)
-        ctx.n_classes = n_classes
         ctx.set_materialize_grads(False)                      # (no zero-filled gradient for the integer matrix: the backward is ONE launch)
         loss = out[0]
         if want_confusion:
@@ -1880,15 +1900,7 @@ class _BalancedCrossEntropy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, *_):
         (g,) = ctx.saved_tensors
-        if g_loss is None:
-            return None, None, None, None
-        lib = _lib.load()
-        g_loss = g_loss.to(torch.float32).contiguous()
-        out = torch.empty_like(g)
-        rc = lib.dgn_node_ce_backward(g.shape[0], ctx.n_classes, g.data_ptr(), g.stride(0), g_loss.data_ptr(), out.data_ptr(), out.stride(0),
-                                      _lib.stream_ptr(g.device))
-        _lib.check(rc, "dgn_node_ce_backward")
-        return out, None, None, None
+        return None if g_loss is None else _loss_backward("dgn_node_ce_backward", g, g_loss), None, None, None, None
 
 
 def balanced_cross_entropy(scores: torch.Tensor, labels: torch.Tensor, n_classes: int, confusion: bool = False):
@@ -1898,7 +1910,7 @@ def balanced_cross_entropy(scores: torch.Tensor, labels: torch.Tensor, n_classes
     (capturable).  Returns the 0-dim loss; with ``confusion=True`` also the ``[C, C]`` int64 device matrix of the reference's
     ``accuracy_SBM`` (train/metrics.py:37-40: rows = label, columns = arg-max over classes of the softmax over the NODES), see
     ``nets.accuracy_sbm``.  One class only among the labels: ``nan``, as the reference."""
-    return _BalancedCrossEntropy.apply(scores, labels, int(n_classes), bool(confusion))
+    return _BalancedCrossEntropy.apply(scores, labels, int(n_classes), bool(confusion), _wants_grad(scores))
 
 
 # ---- OGB molecule nets: multi-column embedding sum, masked BCE with logits (dgn_mol_io.hip) ------------------------------------------
@@ -1945,8 +1957,8 @@ class _MultiEmbedding(torch.autograd.Function):
             idx = idx.contiguous()
         dims = _i32_array([int(w.shape[0]) for w in weights])
         out = torch.empty(N, F, dtype=torch.float32, device=idx.device)
-        rc = lib.dgn_multi_embedding_forward(N, n_cols, F, idx.data_ptr(), idx.stride(0) if N > 1 else n_cols, _ptr_array(weights), dims,
-                                             out.data_ptr(), F, _lib.stream_ptr(idx.device))
+        rc = lib.dgn_multi_embedding_forward(N, n_cols, F, idx.data_ptr(), _ld(idx), _ptr_array(weights), dims, out.data_ptr(), F,
+                                             _lib.stream_ptr(idx.device))
         _lib.check(rc, "dgn_multi_embedding_forward")
         ctx.save_for_backward(idx)
         ctx.dims, ctx.F = dims, F
@@ -1961,9 +1973,9 @@ class _MultiEmbedding(torch.autograd.Function):
         g = g.contiguous()
         grads = [torch.empty(int(d), F, dtype=torch.float32, device=dev) for d in dims]
         ws_bytes = lib.dgn_multi_embedding_backward_workspace_bytes(N, n_cols, dims, F)
-        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
-        rc = lib.dgn_multi_embedding_backward(N, n_cols, F, idx.data_ptr(), idx.stride(0) if N > 1 else n_cols, dims, g.data_ptr(), F,
-                                              _ptr_array(grads), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        ws = _workspace(ws_bytes, torch.float32, dev)
+        rc = lib.dgn_multi_embedding_backward(N, n_cols, F, idx.data_ptr(), _ld(idx), dims, g.data_ptr(), F, _ptr_array(grads), ws.data_ptr(),
+                                              ws_bytes, _lib.stream_ptr(dev))
         _lib.check(rc, "dgn_multi_embedding_backward")
         return (None,) + tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[1:]))
 
@@ -1990,36 +2002,32 @@ def multi_embedding(weights, idx: torch.Tensor) -> torch.Tensor:
     return _MultiEmbedding.apply(idx, *weights)
 
 
-class _MaskedBCE(torch.autograd.Function):
+class _MaskedMean(torch.autograd.Function):
+    """the masked mean losses; ``family``: the entry points' common prefix, ``dgn_masked_bce`` or ``dgn_masked_mae``"""
+
     @staticmethod
-    def forward(ctx, scores, labels):
+    def forward(ctx, scores, targets, family, want_grad):
         lib = _lib.load()
         if scores.stride(1) != 1:
             scores = scores.contiguous()
-        labels = labels.contiguous()
+        targets = targets.contiguous()
         G, T = scores.shape
         dev = scores.device
-        want_grad = ctx.needs_input_grad[0]                   # (False under torch.no_grad(): no gradient buffer is written)
         out = torch.empty(1, dtype=torch.float32, device=dev)
         g = torch.empty(G, T, dtype=torch.float32, device=dev) if want_grad else None
-        ws_bytes = lib.dgn_masked_bce_workspace_bytes(G, T)
-        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
-        rc = lib.dgn_masked_bce_forward(G, T, scores.data_ptr(), scores.stride(0) if G > 1 else T, labels.data_ptr(), T, out.data_ptr(), _ptr(g), T,
-                                        ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-        _lib.check(rc, "dgn_masked_bce_forward")
+        ws_bytes = getattr(lib, family + "_workspace_bytes")(G, T)
+        ws = _workspace(ws_bytes, torch.float64, dev)
+        rc = getattr(lib, family + "_forward")(G, T, scores.data_ptr(), _ld(scores), targets.data_ptr(), T, out.data_ptr(), _ptr(g), T,
+                                               ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        _lib.check(rc, family + "_forward")
         ctx.save_for_backward(g)
+        ctx.family = family
         return out[0]
 
     @staticmethod
     def backward(ctx, g_loss):
         (g,) = ctx.saved_tensors
-        lib = _lib.load()
-        g_loss = g_loss.to(torch.float32).contiguous()
-        out = torch.empty_like(g)
-        rc = lib.dgn_masked_bce_backward(g.shape[0], g.shape[1], g.data_ptr(), g.stride(0), g_loss.data_ptr(), out.data_ptr(), out.stride(0),
-                                         _lib.stream_ptr(g.device))
-        _lib.check(rc, "dgn_masked_bce_backward")
-        return out, None
+        return _loss_backward(ctx.family + "_backward", g, g_loss), None, None, None
 
 
 def masked_bce_with_logits(scores: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
@@ -2037,39 +2045,7 @@ def masked_bce_with_logits(scores: torch.Tensor, labels: torch.Tensor) -> torch.
                          f"{tuple(labels.shape)}")
     if scores.shape[1] == 0:
         raise ValueError("masked_bce_with_logits: at least one task column")
-    return _MaskedBCE.apply(scores, labels.to(torch.float32))
-
-
-class _MaskedL1(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, scores, targets):
-        lib = _lib.load()
-        if scores.stride(1) != 1:
-            scores = scores.contiguous()
-        targets = targets.contiguous()
-        G, T = scores.shape
-        dev = scores.device
-        want_grad = ctx.needs_input_grad[0]                   # (False under torch.no_grad(): no gradient buffer is written)
-        out = torch.empty(1, dtype=torch.float32, device=dev)
-        g = torch.empty(G, T, dtype=torch.float32, device=dev) if want_grad else None
-        ws_bytes = lib.dgn_masked_mae_workspace_bytes(G, T)
-        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
-        rc = lib.dgn_masked_mae_forward(G, T, scores.data_ptr(), scores.stride(0) if G > 1 else T, targets.data_ptr(), T, out.data_ptr(), _ptr(g), T,
-                                       ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-        _lib.check(rc, "dgn_masked_mae_forward")
-        ctx.save_for_backward(g)
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        (g,) = ctx.saved_tensors
-        lib = _lib.load()
-        g_loss = g_loss.to(torch.float32).contiguous()
-        out = torch.empty_like(g)
-        rc = lib.dgn_masked_mae_backward(g.shape[0], g.shape[1], g.data_ptr(), g.stride(0), g_loss.data_ptr(), out.data_ptr(), out.stride(0),
-                                        _lib.stream_ptr(g.device))
-        _lib.check(rc, "dgn_masked_mae_backward")
-        return out, None
+    return _MaskedMean.apply(scores, labels.to(torch.float32), "dgn_masked_bce", _wants_grad(scores))
 
 
 def masked_l1_loss(scores: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
@@ -2089,7 +2065,7 @@ def masked_l1_loss(scores: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
                          f"{tuple(targets.shape)}")
     if scores.shape[1] == 0:
         raise ValueError("masked_l1_loss: at least one target column")
-    return _MaskedL1.apply(scores, targets.to(torch.float32))
+    return _MaskedMean.apply(scores, targets.to(torch.float32), "dgn_masked_mae", _wants_grad(scores))
 
 
 # ---- input stage with positional encodings: embedding sum + Linear on pos_enc (dgn_node_input.hip) ---------------------------------------
@@ -2129,9 +2105,8 @@ class _NodeInput(torch.autograd.Function):
             pos_enc = pos_enc.contiguous()
         dims = _i32_array([int(t.shape[0]) for t in tables])
         out = torch.empty(N, F, dtype=torch.float32, device=idx.device)
-        rc = lib.dgn_node_input_forward(N, n_cols, K, F, idx.data_ptr(), idx.stride(0) if N > 1 else n_cols, _ptr_array(tables), dims,
-                                        pos_enc.data_ptr(), pos_enc.stride(0) if N > 1 else K, weight.data_ptr(), _ptr(bias), out.data_ptr(), F,
-                                        _lib.stream_ptr(idx.device))
+        rc = lib.dgn_node_input_forward(N, n_cols, K, F, idx.data_ptr(), _ld(idx), _ptr_array(tables), dims, pos_enc.data_ptr(), _ld(pos_enc),
+                                        weight.data_ptr(), _ptr(bias), out.data_ptr(), F, _lib.stream_ptr(idx.device))
         _lib.check(rc, "dgn_node_input_forward")
         ctx.save_for_backward(idx, pos_enc)
         ctx.dims, ctx.F, ctx.K = dims, F, K
@@ -2152,10 +2127,9 @@ class _NodeInput(torch.autograd.Function):
             if g.stride(1) != 1:
                 g = g.contiguous()
             ws_bytes = lib.dgn_node_input_backward_workspace_bytes(N, n_cols, dims, K, F)
-            ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
-            rc = lib.dgn_node_input_backward(N, n_cols, K, F, idx.data_ptr(), idx.stride(0) if N > 1 else n_cols, dims, pos_enc.data_ptr(),
-                                             pos_enc.stride(0) if N > 1 else K, g.data_ptr(), g.stride(0) if N > 1 else F, _ptr_array(grads),
-                                             g_w.data_ptr(), _ptr(g_b), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+            ws = _workspace(ws_bytes, torch.float32, dev)
+            rc = lib.dgn_node_input_backward(N, n_cols, K, F, idx.data_ptr(), _ld(idx), dims, pos_enc.data_ptr(), _ld(pos_enc), g.data_ptr(),
+                                             _ld(g), _ptr_array(grads), g_w.data_ptr(), _ptr(g_b), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
             _lib.check(rc, "dgn_node_input_backward")
         need = ctx.needs_input_grad
         return (None, None, g_w if need[2] else None, g_b) + tuple(gr if n else None for gr, n in zip(grads, need[4:]))
@@ -2212,8 +2186,7 @@ class _FeatureEmbedding(torch.autograd.Function):
         R, K = x.shape
         F = weight.shape[0]
         out = torch.empty(R, F, dtype=torch.float32, device=x.device)
-        rc = lib.dgn_feat_embed_forward(R, K, F, x.data_ptr(), x.stride(0) if R > 1 else K, weight.data_ptr(), _ptr(bias), out.data_ptr(), F,
-                                        _lib.stream_ptr(x.device))
+        rc = lib.dgn_feat_embed_forward(R, K, F, x.data_ptr(), _ld(x), weight.data_ptr(), _ptr(bias), out.data_ptr(), F, _lib.stream_ptr(x.device))
         _lib.check(rc, "dgn_feat_embed_forward")
         ctx.save_for_backward(x)
         ctx.F = F
@@ -2233,9 +2206,9 @@ class _FeatureEmbedding(torch.autograd.Function):
         g_w = torch.empty(F, K, dtype=torch.float32, device=dev)
         g_b = torch.empty(F, dtype=torch.float32, device=dev) if want_b else None
         ws_bytes = lib.dgn_feat_embed_backward_workspace_bytes(R, K, F)
-        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
-        rc = lib.dgn_feat_embed_backward(R, K, F, x.data_ptr(), x.stride(0) if R > 1 else K, g.data_ptr(), g.stride(0) if R > 1 else F,
-                                         g_w.data_ptr(), _ptr(g_b), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        ws = _workspace(ws_bytes, torch.float32, dev)
+        rc = lib.dgn_feat_embed_backward(R, K, F, x.data_ptr(), _ld(x), g.data_ptr(), _ld(g), g_w.data_ptr(), _ptr(g_b), ws.data_ptr(), ws_bytes,
+                                         _lib.stream_ptr(dev))
         _lib.check(rc, "dgn_feat_embed_backward")
         return None, g_w, g_b
 
@@ -2268,9 +2241,9 @@ class _ClassCrossEntropy(torch.autograd.Function):
         hits = torch.empty((), dtype=torch.int64, device=dev) if want_hits else None
         g = torch.empty(G, n_classes, dtype=torch.float32, device=dev) if want_grad else None
         ws_bytes = lib.dgn_class_ce_workspace_bytes(G, n_classes)
-        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
-        rc = lib.dgn_class_ce_forward(G, n_classes, scores.data_ptr(), scores.stride(0) if G > 1 else n_classes, labels.data_ptr(), out.data_ptr(),
-                                      _ptr(hits), _ptr(g), n_classes, ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+        ws = _workspace(ws_bytes, torch.float64, dev)
+        rc = lib.dgn_class_ce_forward(G, n_classes, scores.data_ptr(), _ld(scores), labels.data_ptr(), out.data_ptr(), _ptr(hits), _ptr(g),
+                                      n_classes, ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
         _lib.check(rc, "dgn_class_ce_forward")
         ctx.save_for_backward(g)
         ctx.set_materialize_grads(False)                      # (no zero-filled gradient for the integer count: the backward is ONE launch)
@@ -2283,15 +2256,7 @@ class _ClassCrossEntropy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, *_):
         (g,) = ctx.saved_tensors
-        if g_loss is None:
-            return None, None, None, None
-        lib = _lib.load()
-        g_loss = g_loss.to(torch.float32).contiguous()
-        out = torch.empty_like(g)
-        rc = lib.dgn_class_ce_backward(g.shape[0], g.shape[1], g.data_ptr(), g.stride(0), g_loss.data_ptr(), out.data_ptr(), out.stride(0),
-                                       _lib.stream_ptr(g.device))
-        _lib.check(rc, "dgn_class_ce_backward")
-        return out, None, None, None
+        return None if g_loss is None else _loss_backward("dgn_class_ce_backward", g, g_loss), None, None, None
 
 
 def class_cross_entropy(scores: torch.Tensor, labels: torch.Tensor, hits: bool = False):
@@ -2306,9 +2271,7 @@ def class_cross_entropy(scores: torch.Tensor, labels: torch.Tensor, hits: bool =
         raise ValueError(f"class_cross_entropy: scores must be float32 [G, 2 <= C <= {CLASS_CE_MAX_CLASSES}], got {scores.dtype} {tuple(scores.shape)}")
     if labels.dtype != torch.int64 or labels.shape != (scores.shape[0],):
         raise ValueError("class_cross_entropy: labels must be int64 [G]")
-    # (whether a gradient is wanted is decided here: inside Function.forward grad mode is always off and needs_input_grad ignores no_grad --
-    #  under torch.no_grad() no [G, C] gradient buffer is allocated or written)
-    return _ClassCrossEntropy.apply(scores, labels, bool(hits), torch.is_grad_enabled() and scores.requires_grad)
+    return _ClassCrossEntropy.apply(scores, labels, bool(hits), _wants_grad(scores))
 
 
 # ---- the nets' MLPReadout head in one launch per direction (dgn_mlp_head.hip) ---------------------------------------------------------
@@ -2348,8 +2311,8 @@ class _MLPHead(torch.autograd.Function):
         dims = _mlp_head_dims(weights)
         N, dev = x.shape[0], x.device
         y = torch.empty(N, dims[-1], dtype=torch.float32, device=dev)
-        rc = lib.dgn_mlp_head_forward(N, n_lin, _i32_array(dims), x.data_ptr(), x.stride(0) if N > 1 else dims[0], _ptr_array(weights),
-                                      _ptr_array(biases), y.data_ptr(), dims[-1], _lib.stream_ptr(dev))
+        rc = lib.dgn_mlp_head_forward(N, n_lin, _i32_array(dims), x.data_ptr(), _ld(x), _ptr_array(weights), _ptr_array(biases), y.data_ptr(),
+                                      dims[-1], _lib.stream_ptr(dev))
         _lib.check(rc, "dgn_mlp_head_forward")
         ctx.save_for_backward(x, *weights, *biases)           # (x and the parameters only: the backward computes the hidden activations again)
         ctx.dims = dims
@@ -2369,10 +2332,9 @@ class _MLPHead(torch.autograd.Function):
         g_w, g_b = [torch.empty_like(w) for w in weights], [torch.empty_like(b) for b in biases]
         c_dims = _i32_array(dims)
         ws_bytes = lib.dgn_mlp_head_backward_workspace_bytes(N, n_lin, c_dims)
-        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
-        rc = lib.dgn_mlp_head_backward(N, n_lin, c_dims, x.data_ptr(), x.stride(0) if N > 1 else dims[0], _ptr_array(weights), _ptr_array(biases),
-                                       g_y.data_ptr(), dims[-1], _ptr(g_x), dims[0], _ptr_array(g_w), _ptr_array(g_b), ws.data_ptr(), ws_bytes,
-                                       _lib.stream_ptr(dev))
+        ws = _workspace(ws_bytes, torch.float32, dev)
+        rc = lib.dgn_mlp_head_backward(N, n_lin, c_dims, x.data_ptr(), _ld(x), _ptr_array(weights), _ptr_array(biases), g_y.data_ptr(), dims[-1],
+                                       _ptr(g_x), dims[0], _ptr_array(g_w), _ptr_array(g_b), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
         _lib.check(rc, "dgn_mlp_head_backward")
         return (g_x, None) + tuple(g if need else None for g, need in zip(g_w + g_b, ctx.needs_input_grad[2:]))
 
