@@ -18,6 +18,7 @@ from .nets import AtomEncoder, BondEncoder, DGNHIVNet, DGNNet, DGNNodeNet, DGNPC
 from .ops import class_cross_entropy, feature_embedding
 from .nets import DGNSuperpixelNet, accuracy_mnist_cifar
 from .ops import masked_l1_loss, node_input
+from .data import Batch, PackedGraphs
 
 __all__ = ["DGNGraph", "as_dgn_graph", "compute_edge_weights", "make_plan", "directional_aggregate", "FCLayer", "MLP",
            "get_activation", "AGGREGATORS", "SCALERS", "DGNLayer", "DGNLayerSimple", "DGNLayerComplex", "DGNLayerTower",
@@ -26,4 +27,4 @@ __all__ = ["DGNGraph", "as_dgn_graph", "compute_edge_weights", "make_plan", "dir
            "multi_embedding", "masked_bce_with_logits", "mlp_head", "AtomEncoder", "BondEncoder", "DGNHIVNet", "DGNPCBANet", "rocauc_ogb", "ap_ogb",
            "knn_edge_counts", "knn_graph", "coord_encoding", "sort_eig", "superpixel_eig",
            "feature_embedding", "class_cross_entropy", "DGNSuperpixelNet", "accuracy_mnist_cifar",
-           "node_input", "masked_l1_loss"]
+           "node_input", "masked_l1_loss", "PackedGraphs", "Batch"]

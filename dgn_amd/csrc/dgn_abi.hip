@@ -151,7 +151,7 @@ extern "C" size_t dgn_sizeof(const char* name) {
 #define DGN_SZ(T) if (name && !strcmp(name, #T)) return sizeof(T);
     DGN_SZ(DgnGraph) DGN_SZ(DgnChannel) DGN_SZ(DgnAggSpec) DGN_SZ(DgnMsg) DGN_SZ(DgnMsgGrad) DGN_SZ(DgnBnGrad) DGN_SZ(DgnTowersLayer)
     DGN_SZ(DgnTowersGrads) DGN_SZ(DgnDegreeClasses) DGN_SZ(DgnDcLayout) DGN_SZ(DgnDenseLayer) DGN_SZ(DgnDenseGrads) DGN_SZ(DgnBlockTable)
-    DGN_SZ(DgnBlockLayer) DGN_SZ(DgnBlockGrads)
+    DGN_SZ(DgnBlockLayer) DGN_SZ(DgnBlockGrads) DGN_SZ(DgnCollate)
 #undef DGN_SZ
     return 0;
 }

@@ -167,6 +167,42 @@ class DGNGraph:
         self.batch_nodes, self.batch_edges = N, E
         self.invalidate_caches()
 
+    def load_packed(self, ds, ids, node: Optional[dict] = None, edge: Optional[dict] = None, graph: Optional[dict] = None,
+                    g_rows_out: Optional[int] = None, snorm_n: Optional[torch.Tensor] = None, snorm_e: Optional[torch.Tensor] = None,
+                    graph_id: Optional[torch.Tensor] = None):
+        """``rebuild`` from a device-resident dataset (``dgn_amd.data.PackedGraphs``): the graphs ``ids`` of ``ds`` become this padded
+        graph's batch by ONE ``dgn_collate`` launch that cuts the CSR, its transposed view, the statistics, ``n_valid`` and ``eig`` out of
+        the dataset's -- no sort, no scan -- and leaves every array as ``rebuild`` on the batch's edge list would.  ``node`` / ``edge`` /
+        ``graph`` (column name -> static buffer of ``n_cap`` / ``e_cap`` / ``g_rows_out`` rows), ``snorm_n`` / ``snorm_e`` / ``graph_id``:
+        further outputs of the same launch.  The host knows the batch's sizes and its largest in-degree, and the dataset was checked for
+        hub rows when it was packed, so nothing is deferred.  Errors (capacity, shapes) raise before anything is written.  Returns the
+        batch's host-side plan (``G``, ``N``, ``E``, ``sizes``)."""
+        pad = self._pad
+        p = ds.plan(ids)
+        self.check_deferred(final=False)                 # (the batch loaded before this one, as in rebuild)
+        if p.N > pad["n_cap"] or p.E > pad["e_cap"]:
+            raise ValueError(f"batch ({p.N} nodes, {p.E} edges) exceeds the capacity ({pad['n_cap']}, {pad['e_cap']})")
+        blk = self.__dict__.get("_blk_static")
+        if blk is not None:
+            if p.G > blk["n_blocks"]:
+                raise ValueError(f"{p.G} graphs exceed the block table's capacity ({blk['n_blocks']})")
+            if p.G and int(p.sizes.max()) > blk["max_rows"]:
+                raise ValueError(f"a graph of {int(p.sizes.max())} nodes exceeds the block capacity ({blk['max_rows']} rows)")
+        node = dict(node or {})
+        if "eig" in self.ndata:
+            node.setdefault("eig", self.ndata["eig"])
+        csr = dict(indptr=self.indptr, src_csr=self.src, dst_csr=self.dst_csr, eid=self.eid, in_degree=self.in_degree, log_deg=self.log_deg,
+                   csc_ptr=self.csc_ptr, csc_pos=self.csc_pos, csc_order=self._csc_order, stats=self._stats, n_valid=self.n_valid)
+        ds.gather(p, n_rows_out=pad["n_cap"], e_rows_out=pad["e_cap"], g_rows_out=g_rows_out, node=node, edge=edge, graph=graph,
+                  snorm_n=snorm_n, snorm_e=snorm_e, graph_id=graph_id, csr=csr)
+        if blk is not None:
+            self.load_block_sizes(p.sizes)
+        self._stats_pending = False
+        self.max_in_degree = 0                            # (as rebuild leaves it: no launch is skipped on its account)
+        self.batch_nodes, self.batch_edges = p.N, p.E
+        self.invalidate_caches()
+        return p
+
     def check_deferred(self, final: bool = True) -> None:
         """Look at the statistics of the batch loaded last (``rebuild`` without a host sync): raises if it had hub rows, or if a step on
         a static block table met a graph beyond its capacity.  ``final`` (the explicit call after the last batch): the block-overflow

@@ -242,18 +242,26 @@ class CapturedNetStep(_CapturedStep):
     @torch.no_grad()
     def _load_batch(self, src, dst, num_nodes: int, eig, atoms, snorm, sizes, targets, pos_enc=None) -> None:
         """``load`` without the marker behind the batch's target rows."""
-        n_cap, g_cap, dev = self.pb.n_cap, self.g_rows, self.device
         node = self._node_tensors(snorm, pos_enc, type(self).__name__)
         sizes = torch.as_tensor(sizes, dtype=torch.int64)
         G = sizes.numel()
-        if G >= self.g_cap:
-            raise ValueError(f"{G} graphs need a capacity of at least {G + 1} graph rows (rows behind the batch collect the padding)")
-        pad, R = n_cap - int(num_nodes), self.PAD_ROWS
-        if pad > 2048 * R:
-            raise ValueError(f"more than {2048 * R} padding nodes: pick a smaller capacity bucket (a padding row must not be a hub row)")
+        self._check_graph_rows(G, num_nodes)
         self.pb.load(src, dst, num_nodes, eig, node=node, graph_sizes=sizes)
         self.atoms[:num_nodes].copy_(atoms, non_blocking=True)
         self.atoms[num_nodes:].zero_()
+        self._load_readout(sizes, num_nodes)
+        self.targets[:G].copy_(targets, non_blocking=True)
+
+    def _check_graph_rows(self, G: int, num_nodes: int) -> None:
+        if G >= self.g_cap:
+            raise ValueError(f"{G} graphs need a capacity of at least {G + 1} graph rows (rows behind the batch collect the padding)")
+        if self.pb.n_cap - int(num_nodes) > 2048 * self.PAD_ROWS:
+            raise ValueError(f"more than {2048 * self.PAD_ROWS} padding nodes: pick a smaller capacity bucket (a padding row must not be a hub row)")
+
+    def _load_readout(self, sizes: torch.Tensor, num_nodes: int) -> None:
+        """The batch's graph sizes (host int64 tensor) -> the readout CSR."""
+        n_cap, g_cap, G = self.pb.n_cap, self.g_rows, sizes.numel()
+        pad, R = n_cap - int(num_nodes), self.PAD_ROWS
         # graph sizes -> the readout CSR, on the device: ONE copy from a pinned staging buffer (a pageable host tensor copied
         # "non_blocking" right in front of a graph launch stalled the launch by ~20 ms on this runtime), everything else device ops
         h = self._h_sizes
@@ -266,7 +274,24 @@ class CapturedNetStep(_CapturedStep):
         rg.indptr[1:].copy_(torch.cumsum(self._d_sizes, 0))
         rg.in_degree.copy_(self._d_sizes)
         rg.log_deg.copy_(torch.log((self._d_sizes + 1).double()))
-        self.targets[:G].copy_(targets, non_blocking=True)
+
+    @torch.no_grad()
+    def load_packed(self, ds, ids) -> None:
+        """``load`` from a device-resident dataset (``dgn_amd.data.PackedGraphs``): ONE gather launch writes the padded graph's arrays,
+        ``eig``, ``pos_enc``, the graph norm, the features (node column ``feat``) and the targets (graph column ``label``, whose pad value
+        -- NaN, or -1 for classes -- is the marker behind the batch) straight into the static buffers; the readout CSR and the block
+        table follow from the host-known sizes as in ``load``.  A batch beyond the capacity raises before anything is written."""
+        p = ds.plan(ids)
+        self._check_graph_rows(p.G, p.N)
+        marker = ds.pads.get(("graph", "label"))
+        if self.targets.dtype == torch.int64 and marker != -1 or self.targets.dtype != torch.int64 and marker == marker:
+            raise ValueError(f"{type(self).__name__}.load_packed: the dataset's graph column 'label' must pad with "
+                             f"{-1 if self.targets.dtype == torch.int64 else 'NaN'} (the rows the loss masks), not {marker}")
+        node = {"feat": self.atoms}
+        if self.pos_enc_dim > 0:
+            node["pos_enc"] = self.pb.node["pos_enc"]
+        self.pb.graph.load_packed(ds, p, node=node, graph={"label": self.targets}, g_rows_out=self.g_rows, snorm_n=self.snorm)
+        self._load_readout(torch.from_numpy(p.sizes), p.N)
 
     def _step(self) -> None:
         self.opt.zero_grad(set_to_none=True)
@@ -390,6 +415,17 @@ class CapturedNodeStep(_CapturedStep):
         self.feats[num_nodes:].zero_()
         self.labels[:num_nodes].copy_(labels, non_blocking=True)
         self.labels[num_nodes:].fill_(-1)
+
+    @torch.no_grad()
+    def load_packed(self, ds, ids) -> None:
+        """``load`` from a device-resident dataset (``dgn_amd.data.PackedGraphs``; node columns ``feat`` and ``label``, the latter padding
+        with -1): ONE gather launch into the static buffers.  A batch beyond the capacity raises before anything is written."""
+        if ds.pads.get(("node", "label")) != -1:
+            raise ValueError("CapturedNodeStep.load_packed: the dataset's node column 'label' must pad with -1 (the rows the loss masks)")
+        node = {"feat": self.feats, "label": self.labels}
+        if self.pos_enc_dim > 0:
+            node["pos_enc"] = self.pb.node["pos_enc"]
+        self.pb.graph.load_packed(ds, ids, node=node, snorm_n=self.snorm)
 
     def _step(self) -> None:
         self.opt.zero_grad(set_to_none=True)

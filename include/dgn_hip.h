@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DGN_ABI_VERSION 36
+#define DGN_ABI_VERSION 37
 
 #define DGN_MAX_AGG 16     /* aggregators per launch (the host splits longer lists)            */
 #define DGN_MAX_CH 4       /* edge-weight channels per launch                                   */
@@ -502,7 +502,8 @@ int dgn_layer_fused_forward(const DgnGraph* g, const DgnAggSpec* spec, const Dgn
 /* ---- graph batch preparation on the device (dgn_graph_build.hip) ------------------------------------------------------
  * The edge list of a (batched) graph in edge-id order -> the DgnGraph arrays, by a handful of kernels on `stream`, no host
  * synchronisation inside.  Replaces what DGL does per update_all call (degree bucketing, nets/dgn_layer.py:115,186,264) and
- * the ~40 torch ops of the Python build; `dgl.batch` (data/molecules.py:229) is where a caller would invoke it.
+ * the ~40 torch ops of the Python build; `dgl.batch` (data/molecules.py:229) is where a caller invokes it ONCE per
+ * dataset: dgn_amd/data.py builds the packed dataset's CSR with it, and dgn_collate (below) cuts every batch out of that.
  *   dgn_graph_build          indptr [N+1], src_csr / dst_csr [E] (source / destination of every CSR slot; slots of a row in
  *                            ascending edge id), eid [E] (slot -> edge id), log_deg [N], in_degree [N] (int64, may be NULL),
  *                            stats[0] = largest in-degree, stats[1] = rows with more than hub_threshold in-edges
@@ -1020,6 +1021,83 @@ size_t dgn_node_input_backward_workspace_bytes(int64_t n_rows, int32_t n_cols, c
 int dgn_node_input_backward(int64_t n_rows, int32_t n_cols, int32_t k, int32_t F, const int64_t* idx, int64_t ld_idx, const int32_t* dims,
                             const float* pe, int64_t ld_pe, const float* g, int64_t ld_g, float* const* g_tables, float* g_w, float* g_b, void* ws,
                             size_t ws_bytes, void* stream);      /* autograd of the same lines */
+
+/* ---- collate: a batch of a device-resident dataset as ONE gather (dgn_collate.hip) -------------------------------------------
+ * The reference forms every batch on the host (`collate`: data/molecules.py:219-230, data/SBMs.py:167-179, data/HIV.py:113-125,
+ * data/PCBA.py:266-278, data/superpixels.py:316-330: dgl.batch over the samples plus the graph-norm vectors).  Here the dataset
+ * is packed once -- concatenated columns and ONE DgnGraph over all its nodes (dgn_graph_build + dgn_graph_build_csc) -- and, since
+ * the graphs of a batch are disjoint and every graph's nodes, edges, CSR slots and CSC ranks are one contiguous range of the
+ * dataset, a batch's arrays are shifted copies of those ranges.  One kernel launch on `stream`: no host synchronisation, no
+ * workspace, no library call, every launch parameter a function of the sizes.
+ *   table        DEVICE int32 [5][G + 1] (rows: batch node offset, batch edge offset, dataset node base, dataset edge base, dataset
+ *                graph id; the offsets' entry G is N resp. E, the other rows' entry G is not read).  The host computes it (the batch's
+ *                graph ids are host-known) and uploads it with one copy.
+ *   d_*          the dataset: its DgnGraph arrays, its edge list in edge-id order (int64, dataset node ids), the per-GRAPH graph-norm
+ *                values (the kernel only broadcasts them, so they carry the reference's own host arithmetic bit for bit)
+ *   columns      *_in [c] a dataset column of *_row_bytes [c] bytes per row (a multiple of 4), *_out [c] its batch rows (NULL: not
+ *                wanted), *_pad [c] the 8-byte pattern of the rows behind the batch (even dwords of a row take its low half, odd ones
+ *                its high half: 0, -1 and two copies of a float's bits all fit).  Host arrays, they travel in the kernel arguments.
+ *   outputs      each optional (NULL = not wanted) and written for the FULL capacity n_rows_out >= N, e_rows_out >= E, g_rows_out >= G:
+ *                column rows; snorm_n / snorm_e (0 behind the batch); graph_id (int32, -1 behind); src / dst (int64, edge-id order,
+ *                batch node ids; 0 behind); and the batch's DgnGraph arrays exactly as dgn_graph_build + dgn_graph_build_csc on that
+ *                edge list with n_nodes = n_rows_out leave them: indptr / csc_ptr [n_rows_out + 1] (= E from row N on), src_csr /
+ *                dst_csr / eid / csc_pos / csc_order [e_rows_out] (0 behind), in_degree / log_deg [n_rows_out] (0 behind), stats
+ *                int32 [4] = (max_in_degree, 0, 0, 0), n_valid int64 [1] = N.
+ * 1 <= G <= 65 535 graphs of any size within the int32 totals; G == 0 or N == 0: DGN_OK, the pad values everywhere.  More columns
+ * than the limits below, a row width that is no multiple of 4, capacities below the batch: DGN_ERR_INVALID, nothing launched. */
+#define DGN_COLLATE_MAX_NODE_COLS 8
+#define DGN_COLLATE_MAX_EDGE_COLS 4
+#define DGN_COLLATE_MAX_GRAPH_COLS 2
+#define DGN_COLLATE_MAX_GRAPHS 65535
+typedef struct DgnCollate {
+    int64_t n_graphs, n_nodes, n_edges;              /* the batch: G, N, E                                            */
+    int64_t n_rows_out, e_rows_out, g_rows_out;      /* rows of every per-node / per-edge / per-graph output           */
+    const int32_t* table;
+    const int32_t* d_indptr;
+    const int32_t* d_src;
+    const int32_t* d_dst_csr;
+    const int64_t* d_eid;
+    const int64_t* d_in_degree;
+    const float* d_log_deg;
+    const int32_t* d_csc_ptr;
+    const int32_t* d_csc_pos;
+    const int32_t* d_csc_order;
+    const int64_t* d_edge_src;
+    const int64_t* d_edge_dst;
+    const float* d_snorm_n;
+    const float* d_snorm_e;
+    int32_t n_node_cols, n_edge_cols, n_graph_cols;
+    int32_t max_in_degree;                           /* of the batch (host-known: the largest of its graphs')          */
+    const void* node_in[DGN_COLLATE_MAX_NODE_COLS];
+    void* node_out[DGN_COLLATE_MAX_NODE_COLS];
+    int64_t node_pad[DGN_COLLATE_MAX_NODE_COLS];
+    int32_t node_row_bytes[DGN_COLLATE_MAX_NODE_COLS];
+    const void* edge_in[DGN_COLLATE_MAX_EDGE_COLS];
+    void* edge_out[DGN_COLLATE_MAX_EDGE_COLS];
+    int64_t edge_pad[DGN_COLLATE_MAX_EDGE_COLS];
+    int32_t edge_row_bytes[DGN_COLLATE_MAX_EDGE_COLS];
+    const void* graph_in[DGN_COLLATE_MAX_GRAPH_COLS];
+    void* graph_out[DGN_COLLATE_MAX_GRAPH_COLS];
+    int64_t graph_pad[DGN_COLLATE_MAX_GRAPH_COLS];
+    int32_t graph_row_bytes[DGN_COLLATE_MAX_GRAPH_COLS];
+    float* snorm_n;
+    float* snorm_e;
+    int32_t* graph_id;
+    int64_t* src;
+    int64_t* dst;
+    int32_t* indptr;
+    int32_t* src_csr;
+    int32_t* dst_csr;
+    int64_t* eid;
+    int64_t* in_degree;
+    float* log_deg;
+    int32_t* csc_ptr;
+    int32_t* csc_pos;
+    int32_t* csc_order;
+    int32_t* stats;
+    int64_t* n_valid;
+} DgnCollate;
+int dgn_collate(const DgnCollate* c, void* stream);
 
 #ifdef __cplusplus
 }
