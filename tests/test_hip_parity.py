@@ -878,27 +878,67 @@ def test_towers_backward_with_the_one_pass_pretrans_backward_is_bitwise_the_two_
     weight / bias gradient in ONE pass over d(P|Q) against bd_backward_input + bd_wgrad -- the input gradient has the same bits (same MFMAs in
     the same order per output); the weight gradient's partial sums meet in another order (fp32 rounding), reproducibly (partial last strips
     and a single-graph batch included)."""
+    from dgn_amd import synth
+    _one_pass_pretrans_backward_vs_the_two_kernels(monkeypatch, 70, 5, residual, synth.molecule_batch(n_graphs, seed=31, laplacian_eig=False))
+
+
+_LOOP_BATCH = {}
+
+
+def _looping_molecule_batch():
+    """A batch whose 16-row strips outnumber three times the waves bd_backward_both can have: its workgroups number at most the CU count,
+    eight waves each (csrc/dgn_linear_bd.hip), so from 16 * 3 * 8 * CUs nodes on every wave owns at least three strips -- the first, the
+    middle and the last iteration of its loop all run.  From the hardware's size, not from the plan under test; built once."""
+    from dgn_amd import synth
+    need = 16 * 3 * 8 * torch.cuda.get_device_properties(0).multi_processor_count
+    if "b" not in _LOOP_BATCH:
+        _LOOP_BATCH["b"] = synth.molecule_batch(need // 20 + 1, seed=31, laplacian_eig=False)      # (9 .. 37 nodes a graph, 23 on average)
+    assert int(_LOOP_BATCH["b"]["num_nodes"]) > need
+    return _LOOP_BATCH["b"]
+
+
+# the five instances of bd_backward_both: the DGN_BD_SHAPES with f_in <= 16 as (hidden, towers)
+@pytest.mark.parametrize("hidden,towers", [(70, 5), (50, 5), (60, 5), (56, 4), (28, 2)])
+@pytest.mark.parametrize("batch", ["37 graphs", "looping"])
+def test_towers_backward_one_pass_pretrans_backward_every_instance(monkeypatch, hidden, towers, batch):
+    """The asserts of the test above on every instantiated (towers, f_in) pair, on a small batch and on one large enough that the kernel's
+    waves loop; and the fused pass' pretrans weight gradient against fp64 (see the helper)."""
+    from dgn_amd import synth
+    b = synth.molecule_batch(37, seed=31, laplacian_eig=False) if batch == "37 graphs" else _looping_molecule_batch()
+    _one_pass_pretrans_backward_vs_the_two_kernels(monkeypatch, hidden, towers, True, b, check_fp64=True)
+
+
+def _one_pass_pretrans_backward_vs_the_two_kernels(monkeypatch, F_, towers, residual, b, check_fp64=False):
+    """check_fp64: the gradient of the assembled pretrans operand w_sd [2 Fm, Fm] that the fused pass returns against g^T h in fp64 masked to
+    the towers' diagonal blocks -- g, the gradient at the P|Q product, is the one the per-kernel route hands to its block-diagonal node (the
+    whole-layer call never exposes its own) -- by the rule of _as_good: within 1e-5 max|ref|, or no further from fp64 than four times the
+    two-kernel route; everything outside the blocks exactly zero."""
     dev = _dev()
     import copy
     import dgn_amd
-    from dgn_amd import _lib, synth
+    from dgn_amd import _lib
     monkeypatch.setattr(dgn_amd.ops, "LINEAR_MIN_ROWS", 0)
     monkeypatch.setattr(dgn_amd.ops, "WHOLE_LAYER_MIN_ROWS", 0)
-    b = synth.molecule_batch(n_graphs, seed=31, laplacian_eig=False)
     N = int(b["num_nodes"])
     graph = dgn_amd.DGNGraph(b["src"].to(dev), b["dst"].to(dev), N, eig=b["eig"].to(dev))
-    F_ = 70
     torch.manual_seed(6)
     layer = dgn_amd.DGNLayer(F_, F_, 0.0, True, True, "mean max min dir1-av dir1-dx", "identity amplification attenuation", {"log": torch.tensor(1.1)},
-                             "towers", residual, towers=5, edge_features=False, edge_dim=0).model.to(dev)
+                             "towers", residual, towers=towers, edge_features=False, edge_dim=0).model.to(dev)
     gen = torch.Generator(device=dev).manual_seed(8)
     h0 = torch.randn(N, F_, device=dev, generator=gen)
     ct = torch.randn(N, F_, device=dev, generator=gen)
     snorm = b["snorm_n"].to(dev)
     res = {}
     used = []
+    g_w_sd = {}
     orig = dgn_amd.dgn_layer.towers_layer
-    monkeypatch.setattr(dgn_amd.dgn_layer, "towers_layer", lambda *a, **k: (used.append(1), orig(*a, **k))[1])
+
+    def spy(*a, **k):
+        used.append(1)
+        if check_fp64 and a[10].requires_grad:                                   # (w_sd: the assembled [2 Fm, Fm] operand)
+            a[10].register_hook(lambda gr, key=len(used): g_w_sd.__setitem__(key, gr.detach().clone()))
+        return orig(*a, **k)
+    monkeypatch.setattr(dgn_amd.dgn_layer, "towers_layer", spy)
     for fused in (1, 0):
         monkeypatch.setattr(_lib.options, "bd_bwd_fused", fused)
         lay = copy.deepcopy(layer).train()
@@ -924,6 +964,33 @@ def test_towers_backward_with_the_one_pass_pretrans_backward_is_bitwise_the_two_
     assert torch.equal(h.grad, ga)
     for k, v in lay.named_parameters():
         assert torch.equal(v.grad, pa[k]), k
+    if not check_fp64:
+        return
+    # the per-kernel route: its block-diagonal node receives g, the gradient at the P|Q product
+    seen = {}
+    pair = dgn_amd.ops.pair_linear
+
+    def spy_pair(x, *a, **k):
+        pq = pair(x, *a, **k)
+        pq.register_hook(lambda gr: seen.__setitem__("g", gr.detach().clone()))
+        return pq
+    monkeypatch.setattr(dgn_amd.ops, "pair_linear", spy_pair)
+    monkeypatch.setattr(dgn_amd.ops, "WHOLE_LAYER", False)
+    lay = copy.deepcopy(layer).train()
+    h = h0.clone().requires_grad_(True)
+    lay(graph, h, None, snorm).backward(ct)
+    assert len(used) == 3 and "g" in seen, "the per-kernel route did not run its block-diagonal node"
+    fi, Fm = F_ // towers, F_
+    blocks = torch.zeros(2 * Fm, Fm, dtype=torch.bool, device=dev)
+    for j in range(2):
+        for t in range(towers):
+            blocks[j * Fm + t * fi:j * Fm + (t + 1) * fi, t * fi:(t + 1) * fi] = True
+    ref = (seen["g"].double().t() @ h0.double()) * blocks
+    fused_w, two_w = g_w_sd[1], g_w_sd[2]                                        # (calls 1 and 2: bd_bwd_fused = 1, 0)
+    assert float(fused_w[~blocks].abs().max()) == 0.0
+    scale = float(ref.abs().max())
+    err, err_two = float((fused_w.double() - ref).abs().max()), float((two_w.double() - ref).abs().max())
+    assert err <= 1e-5 * scale or err <= 4.0 * err_two, (err / scale, err_two / scale)
 
 
 @pytest.mark.parametrize("n_graphs,graph_norm", [(200, True), (37, False), (1, True)])

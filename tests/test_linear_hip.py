@@ -494,17 +494,31 @@ def test_mixing_backward_kernels_of_round_6_vs_the_separate_passes(M, n, fo, wit
     assert torch.equal(got, want), float((got - want).abs().max())
 
 
-@pytest.mark.parametrize("T,fi,M", [(5, 14, 4099), (5, 14, 16), (5, 14, 1), (5, 10, 700), (5, 20, 1033), (5, 30, 515), (4, 14, 2000), (2, 14, 333)])
+# every (towers, f_in) pair of DGN_BD_SHAPES (csrc/dgn_linear_bd.hip)
+BD_SHAPES = [(5, 14), (5, 10), (5, 12), (5, 18), (5, 20), (5, 22), (5, 24), (5, 26), (5, 28), (5, 30), (4, 14), (2, 14)]
+
+
+def _long_rows():
+    """16 * 3 * 32 * CUs + 5 rows: a CU holds at most 32 waves (the block-diagonal kernels place at most 16, the weight gradients 8), so every
+    wave of any launch plan owns at least three 16-row strips -- the persistent loops' first, middle and last iterations all run -- and the
+    last strip is partial.  From the hardware's limit, not from the plan under test."""
+    return 16 * 3 * 32 * torch.cuda.get_device_properties(0).multi_processor_count + 5
+
+
+@pytest.mark.parametrize("T,fi,M", [(5, 14, 4099), (5, 14, 16), (5, 14, 1), (5, 10, 700), (5, 20, 1033), (5, 30, 515), (4, 14, 2000), (2, 14, 333)]
+                         + [(T, fi, M) for T, fi in BD_SHAPES for M in (37, -1)])            # (-1: _long_rows())
 def test_block_diagonal_pair_linear_vs_fp64(T, fi, M):
     """dgn_linear_bd_*: the towers' block-diagonal P|Q product, its input gradient (with the two-operand add epilogue) and its weight /
     bias gradient against an fp64 evaluation of the dense formula; off-diagonal weight-gradient blocks are exactly zero; the dense
-    streaming kernels agree; run-to-run bitwise equality."""
+    streaming kernels agree; run-to-run bitwise equality.  Every instantiated shape, at 37 rows and at a row count where every wave loops."""
     import ctypes as C
     import dgn_amd
     from dgn_amd import _lib, ops
     dev = torch.device("cuda")
     lib = _lib.load()
     assert lib.dgn_linear_bd_supported(T, fi)
+    if M < 0:
+        M = _long_rows()
     Fm = T * fi
     gen = torch.Generator(device=dev).manual_seed(T * 100 + fi)
     x = torch.randn(M, Fm, device=dev, generator=gen)
@@ -558,3 +572,61 @@ def test_block_diagonal_pair_linear_vs_fp64(T, fi, M):
         assert bool(bad[2].any()) and not bool(bad[torch.arange(M, device=dev) != 2].any())
         cols = torch.nonzero(bad[2]).flatten()
         assert bool(((cols % Fm) < fi).all())                                           # tower 0's outputs only (P and Q halves)
+
+
+@pytest.mark.parametrize("T,fi", BD_SHAPES)
+def test_block_diagonal_kernels_with_padded_weight_buffers_and_empty_batches(T, fi):
+    """w and dw in buffers wider than T * f_in (ldw = lddw = Fm + 4) whose padding -- and, for w, whose off-diagonal blocks -- hold NaN: the
+    padding is never read (every result is finite and within the bounds of the fp64 test above) and never written (dw's stays NaN).
+    n_rows == 0: the products return at once with their outputs untouched, the weight gradient zero-fills dw's [2 Fm, Fm] and dbias."""
+    from dgn_amd import _lib
+    dev = torch.device("cuda")
+    lib = _lib.load()
+    M, Fm = 37, T * fi
+    ld = Fm + 4
+    gen = torch.Generator(device=dev).manual_seed(T * 100 + fi + 1)
+    x = torch.randn(M, Fm, device=dev, generator=gen)
+    g = torch.randn(M, 2 * Fm, device=dev, generator=gen)
+    bias = torch.randn(2 * Fm, device=dev, generator=gen)
+    blocks = torch.randn(2, T, fi, fi, device=dev, generator=gen)
+    wbuf = torch.full((2 * Fm, ld), float("nan"), device=dev)
+    w0 = torch.zeros(2 * Fm, Fm, device=dev)                      # the same operand with zeros for the reference
+    for j in range(2):
+        for t in range(T):
+            rows, cols = slice(j * Fm + t * fi, j * Fm + (t + 1) * fi), slice(t * fi, (t + 1) * fi)
+            wbuf[rows, cols] = blocks[j, t]
+            w0[rows, cols] = blocks[j, t]
+    st = torch.cuda.current_stream(dev).cuda_stream
+    tol = lambda ref: 2e-6 * float(ref.abs().max()) + 1e-30
+    y = torch.full((M + 16, 2 * Fm), float("nan"), device=dev)
+    _lib.check(lib.dgn_linear_bd_forward(M, T, fi, x.data_ptr(), wbuf.data_ptr(), ld, bias.data_ptr(), y.data_ptr(), st), "dgn_linear_bd_forward")
+    y_ref = x.double() @ w0.double().t() + bias.double()
+    assert float((y[:M].double() - y_ref).abs().max()) <= tol(y_ref)
+    assert bool(torch.isnan(y[M:]).all())
+    gx = torch.full((M + 16, Fm), float("nan"), device=dev)
+    _lib.check(lib.dgn_linear_bd_backward_input(M, T, fi, g.data_ptr(), wbuf.data_ptr(), ld, None, None, gx.data_ptr(), st), "dgn_linear_bd_backward_input")
+    gx_ref = g.double() @ w0.double()
+    assert float((gx[:M].double() - gx_ref).abs().max()) <= tol(gx_ref)
+    assert bool(torch.isnan(gx[M:]).all())
+    nb = lib.dgn_linear_bd_wgrad_workspace_bytes(M, T, fi)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    dw = torch.full((2 * Fm, ld), float("nan"), device=dev)
+    db = torch.full((2 * Fm + 16,), float("nan"), device=dev)
+    _lib.check(lib.dgn_linear_bd_wgrad(M, T, fi, g.data_ptr(), x.data_ptr(), dw.data_ptr(), ld, db.data_ptr(), ws.data_ptr(), nb, st), "dgn_linear_bd_wgrad")
+    mask = (w0 != 0).double()
+    gw_ref = (g.double().t() @ x.double()) * mask
+    assert float((dw[:, :Fm].double() - gw_ref).abs().max()) <= 1e-5 * float(gw_ref.abs().max()) + 1e-30
+    assert float((dw[:, :Fm] * (1 - mask.float())).abs().max()) == 0.0
+    assert bool(torch.isnan(dw[:, Fm:]).all())
+    gb_ref = g.double().sum(0)
+    assert float((db[:2 * Fm].double() - gb_ref).abs().max()) <= 1e-5 * max(1.0, float(gb_ref.abs().max()))
+    assert bool(torch.isnan(db[2 * Fm:]).all())
+    # the empty batch
+    y.fill_(float("nan")), gx.fill_(float("nan")), dw.fill_(float("nan")), db.fill_(float("nan"))
+    _lib.check(lib.dgn_linear_bd_forward(0, T, fi, x.data_ptr(), wbuf.data_ptr(), ld, bias.data_ptr(), y.data_ptr(), st), "dgn_linear_bd_forward")
+    _lib.check(lib.dgn_linear_bd_backward_input(0, T, fi, g.data_ptr(), wbuf.data_ptr(), ld, None, None, gx.data_ptr(), st), "dgn_linear_bd_backward_input")
+    assert lib.dgn_linear_bd_wgrad_workspace_bytes(0, T, fi) == 0
+    _lib.check(lib.dgn_linear_bd_wgrad(0, T, fi, None, None, dw.data_ptr(), ld, db.data_ptr(), None, 0, st), "dgn_linear_bd_wgrad")
+    assert bool(torch.isnan(y).all()) and bool(torch.isnan(gx).all())
+    assert float(dw[:, :Fm].abs().max()) == 0.0 and bool(torch.isnan(dw[:, Fm:]).all())
+    assert float(db[:2 * Fm].abs().max()) == 0.0 and bool(torch.isnan(db[2 * Fm:]).all())
