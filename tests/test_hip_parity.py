@@ -1055,7 +1055,12 @@ def test_towers_forward_with_batchnorm_statistics_from_the_posttrans_epilogue(mo
 
 @pytest.mark.parametrize("type_net,F_,scalers,n_graphs", [("simple", 75, "identity amplification attenuation", 150), ("simple", 70, "identity amplification attenuation", 37),
                                                          ("simple", 65, "identity", 150), ("complex", 46, "identity amplification attenuation", 90),
-                                                         ("complex", 45, "identity", 3)])
+                                                         ("complex", 45, "identity", 3),
+                                                         # tile widths NQ 1, 2, 4, 6 of dc_tile's statistics epilogue (the rows above: NQ 5 and 3) on dc_gemm_small ...
+                                                         ("simple", 16, "identity amplification attenuation", 150), ("simple", 24, "identity amplification attenuation", 37),
+                                                         ("simple", 64, "identity amplification attenuation", 150), ("simple", 90, "identity amplification attenuation", 37),
+                                                         # ... and ~73 000 nodes in ~1 150 units, more than four per CU: dc_gemm<2> / <6> deliver the sums, one slot per range of three units
+                                                         ("simple", 24, "identity amplification attenuation", 3200), ("simple", 90, "identity amplification attenuation", 3200)])
 def test_dense_layer_forward_with_batchnorm_statistics_from_the_posttrans_pass(monkeypatch, type_net, F_, scalers, n_graphs):
     """Round 6 (option bn_stats_fused on the simple / complex whole-layer call): BatchNorm's column sums of the posttrans output ride in the
     degree-class product's epilogue (csrc/dgn_dc_kernels.hpp dc_tile: DcGemmParams.bn_part -- three scalers) or in the scale-combine pass
