@@ -107,24 +107,8 @@ void fill_params(AggParams& p, const DgnGraph* g, const DgnAggSpec* spec, const 
     p.n_ch = spec->n_ch; p.n_scalers = spec->n_scalers; p.n_towers = spec->n_towers;
     p.tower_stride = spec->tower_stride > 0 ? spec->tower_stride : (int64_t)spec->n_scalers * p.agg_total * p.Ft;
     p.avg_log = spec->avg_log; p.eps = spec->eps;
-    uint32_t need = 0;
-    for (int a = 0; a < spec->n_agg; ++a) {
-        const int op = spec->agg_op[a], c = spec->agg_ch[a];
-        p.op_pack |= (uint64_t)op << (4 * a);
-        p.ch_pack |= (uint64_t)((op >= DGN_AGG_DIR_AV && op <= DGN_AGG_DIR_DX_NO_ABS) ? c : 0) << (3 * a);
-        switch (op) {
-            case DGN_AGG_MAX: need |= NEED_MAX | NEED_RECOMP; break;
-            case DGN_AGG_MIN: need |= NEED_MIN | NEED_RECOMP; break;
-            case DGN_AGG_STD: case DGN_AGG_VAR: need |= NEED_SQ | NEED_RECOMP | NEED_M_EMIT; break;
-            case DGN_AGG_DIR_AV: p.any_av = true; break;
-            case DGN_AGG_DIR_WSUM: break;
-            case DGN_AGG_DIR_DX: need |= NEED_XIN | NEED_RECOMP; break;
-            case DGN_AGG_DIR_DX_NO_ABS: need |= NEED_XIN; break;
-            case DGN_AGG_X_IN: need |= NEED_XIN | NEED_XPASS; break;
-        }
-    }
-    for (int s = 0; s < spec->n_scalers; ++s) p.scaler_pack |= (uint32_t)spec->scaler[s] << (2 * s);
-    p.need = need;
+    pack_agg_list(p, spec);
+    pack_scalers(p, spec);
     p.n_slots = n_slots_for(spec);
     p.n_coef = n_coef_for(spec);
 }
@@ -254,17 +238,13 @@ static bool agg_aux_supported(const AggParams& p, const DgnMsg* msg) {
 static bool agg_aux_is_rows(const AggParams& p) { return !short_rows(p); }
 
 extern "C" int dgn_agg_f_valid_supported(const DgnAggSpec* spec) {
-    // (the lists with Cfg::ODD kernels, dgn_agg_kernels.hpp: odd_width_list; one identity scaler, the whole list in one launch, one tower)
-    static const bool no_hot = getenv("DGN_NO_HOT") != nullptr;
-    if (!spec || no_hot || spec->n_towers != 1 || spec->n_scalers != 1 || spec->scaler[0] != DGN_SCALE_IDENTITY ||
+    // (the lists with Cfg::ODD kernels, dgn_agg_kernels.hpp: HotList::odd_width(); one identity scaler, the whole list in one launch, one tower)
+    if (!spec || spec->n_agg < 1 || spec->n_agg > DGN_MAX_AGG || spec->n_towers != 1 || spec->n_scalers != 1 || spec->scaler[0] != DGN_SCALE_IDENTITY ||
         (spec->agg_total > 0 && (spec->agg_offset != 0 || spec->agg_total != spec->n_agg))) return 0;
-    uint64_t ops = 0, chs = 0;
-    for (int a = 0; a < spec->n_agg; ++a) {
-        const int op = spec->agg_op[a];
-        ops |= (uint64_t)op << (4 * a);
-        chs |= (uint64_t)((op >= DGN_AGG_DIR_AV && op <= DGN_AGG_DIR_DX_NO_ABS) ? spec->agg_ch[a] : 0) << (3 * a);
-    }
-    return odd_width_list(spec->n_agg, ops, chs) && spec->n_ch == (spec->n_agg == 2 ? 1 : 2) ? 1 : 0;
+    AggParams p{};
+    p.n_agg = p.agg_total = spec->n_agg; p.n_ch = spec->n_ch; p.n_scalers = 1;
+    pack_agg_list(p, spec);
+    return with_hot_list(p, 0, [](auto h) { return (int)decltype(h)::odd_width(); });
 }
 
 extern "C" size_t dgn_agg_aux_bytes(const DgnGraph* g, const DgnAggSpec* spec, const DgnMsg* msg) {

@@ -107,21 +107,14 @@ int launch_backward_block_cfg(const AggParams& p, int gap, hipStream_t stream) {
 
 template <int VEC>
 int launch_block_vec(const AggParams& p, int gap, hipStream_t stream) {
-    static const bool no_hot = getenv("DGN_NO_HOT") != nullptr;
-    if (no_hot) return 1;
-#define DGN_HOT(NA, OPS, CHS, NS, SCS, N, S, A)                                                                  \
-    if (p.n_agg == NA && p.op_pack == OPS && p.ch_pack == CHS && p.n_scalers == NS && p.scaler_pack == SCS &&    \
-        p.agg_total == NA && p.agg_offset == 0 && p.n_ch == N) {                                                 \
-        using O = StaticOps<NA, OPS, CHS, NS, SCS>;                                                              \
-        if (p.Fv != p.F) {                                                                                       \
-            if constexpr (VEC == 2 && odd_width_list(NA, OPS, CHS)) return launch_backward_block_cfg<Cfg<VEC, N, S, A, true>, O>(p, gap, stream); \
-            return 1;                                                                                            \
-        }                                                                                                        \
-        return launch_backward_block_cfg<Cfg<VEC, N, S, A>, O>(p, gap, stream);                                  \
-    }
-#include "dgn_agg_hot.hpp"
-#undef DGN_HOT
-    return 1;
+    return with_hot_list(p, 1, [&](auto h) {
+        using H = decltype(h);
+        if (p.Fv != p.F) {
+            if constexpr (VEC == 2 && H::odd_width()) return launch_backward_block_cfg<Cfg<VEC, H::NCH, H::STATS, H::AV, true>, typename H::Ops>(p, gap, stream);
+            return 1;
+        }
+        return launch_backward_block_cfg<Cfg<VEC, H::NCH, H::STATS, H::AV>, typename H::Ops>(p, gap, stream);
+    });
 }
 
 }  // namespace dgn

@@ -190,17 +190,10 @@ int launch_backward_graph_cfg(const AggParams& p, hipStream_t stream) {
 }
 
 inline int launch_graph_v2(const AggParams& p, hipStream_t stream) {
-    static const bool no_hot = getenv("DGN_NO_HOT") != nullptr;
-    if (no_hot) return 1;
-#define DGN_HOT(NA, OPS, CHS, NS, SCS, N, S, A)                                                                  \
-    if (p.n_agg == NA && p.op_pack == OPS && p.ch_pack == CHS && p.n_scalers == NS && p.scaler_pack == SCS &&    \
-        p.agg_total == NA && p.agg_offset == 0 && p.n_ch == N) {                                                 \
-        using O = StaticOps<NA, OPS, CHS, NS, SCS>;                                                              \
-        return launch_backward_graph_cfg<Cfg<2, N, S, A>, O>(p, stream);                                         \
-    }
-#include "dgn_agg_hot.hpp"
-#undef DGN_HOT
-    return 1;
+    return with_hot_list(p, 1, [&](auto h) {
+        using H = decltype(h);
+        return launch_backward_graph_cfg<Cfg<2, H::NCH, H::STATS, H::AV>, typename H::Ops>(p, stream);
+    });
 }
 
 }  // namespace dgn

@@ -133,6 +133,34 @@ struct AggParams {
     int32_t blk_lo, blk_hi;
 };
 
+// The single definition of how a DgnAggSpec's aggregator list becomes op_pack / ch_pack / any_av / need (every host route that fills an
+// AggParams calls it; n_agg in 1..DGN_MAX_AGG is the caller's check).  The scalers are packed apart: routes that apply them outside
+// the sweep leave scaler_pack at zero.
+inline void pack_agg_list(AggParams& p, const DgnAggSpec* spec) {
+    p.op_pack = p.ch_pack = 0; p.any_av = false;
+    uint32_t need = 0;
+    for (int a = 0; a < spec->n_agg; ++a) {
+        const int op = spec->agg_op[a], c = spec->agg_ch[a];
+        p.op_pack |= (uint64_t)op << (4 * a);
+        p.ch_pack |= (uint64_t)((op >= DGN_AGG_DIR_AV && op <= DGN_AGG_DIR_DX_NO_ABS) ? c : 0) << (3 * a);
+        switch (op) {
+            case DGN_AGG_MAX: need |= NEED_MAX | NEED_RECOMP; break;
+            case DGN_AGG_MIN: need |= NEED_MIN | NEED_RECOMP; break;
+            case DGN_AGG_STD: case DGN_AGG_VAR: need |= NEED_SQ | NEED_RECOMP | NEED_M_EMIT; break;
+            case DGN_AGG_DIR_AV: p.any_av = true; break;
+            case DGN_AGG_DIR_WSUM: break;
+            case DGN_AGG_DIR_DX: need |= NEED_XIN | NEED_RECOMP; break;
+            case DGN_AGG_DIR_DX_NO_ABS: need |= NEED_XIN; break;
+            case DGN_AGG_X_IN: need |= NEED_XIN | NEED_XPASS; break;
+        }
+    }
+    p.need = need;
+}
+inline void pack_scalers(AggParams& p, const DgnAggSpec* spec) {
+    p.scaler_pack = 0;
+    for (int s = 0; s < spec->n_scalers; ++s) p.scaler_pack |= (uint32_t)spec->scaler[s] << (2 * s);
+}
+
 // accumulator slot ids in the hub workspace
 constexpr int SLOT_SUM = 0, SLOT_SQ = 1, SLOT_MAX = 2, SLOT_MIN = 3, SLOT_AMAX = 4, SLOT_AMIN = 5, SLOT_W0 = 6;
 // coefficient slot ids (backward hub path)
@@ -2148,34 +2176,61 @@ int launch_backward_cfg(const AggParams& p, unsigned tiles, hipStream_t stream) 
     return DGN_OK;
 }
 
-// the baked-in lists that have kernels for rows of an odd width (Cfg::ODD): the simple layers of the reference's configs at odd hidden
-// sizes -- mean dir1-dx-no-abs (ZINC simple, hidden 75) and mean dir1-dx dir2-dx (CIFAR10 / MNIST, hidden 65)
-constexpr bool odd_width_list(int na, uint64_t ops, uint64_t chs) { return (na == 2 && ops == 0x90ull && chs == 0x0ull) || (na == 3 && ops == 0x880ull && chs == 0x40ull); }
+// ---- the baked-in aggregator lists on the host ---------------------------------------------------
+// One row of the generated table dgn_agg_hot.hpp as a type: the list's StaticOps policy and its accumulator configuration.
+template <int NA_, uint64_t OPS, uint64_t CHS, int NS_, uint32_t SCS, int NCH_, bool STATS_, bool AV_>
+struct HotList {
+    static constexpr int NA = NA_, NS = NS_, NCH = NCH_;
+    static constexpr bool STATS = STATS_, AV = AV_;
+    using Ops = StaticOps<NA_, OPS, CHS, NS_, SCS>;
+    template <class... T> static constexpr bool is(T... op) {      // the list, by op name
+        int a = 0; uint64_t pack = 0;
+        ((pack |= (uint64_t)op << (4 * a++)), ...);
+        return a == NA_ && pack == OPS;
+    }
+    // the lists that have kernels for rows of an odd width (Cfg::ODD): the simple layers of the reference's configs at odd hidden
+    // sizes -- mean dir1-dx-no-abs (ZINC simple, hidden 75) and mean dir1-dx dir2-dx (CIFAR10 / MNIST, hidden 65)
+    static constexpr bool odd_width() { return is(DGN_AGG_MEAN, DGN_AGG_DIR_DX_NO_ABS) || (is(DGN_AGG_MEAN, DGN_AGG_DIR_DX, DGN_AGG_DIR_DX) && NCH_ == 2); }
+};
+
+// DGN_NO_HOT (presence = off, read once per process): generic kernels instead of the baked-in lists, on every route
+inline bool hot_lists_on() {
+    static const bool on = getenv("DGN_NO_HOT") == nullptr;
+    return on;
+}
+
+// The one matcher of the table: fn(HotList<...>{}) of the row the launch's (list, scalers, channels) equals -- the whole list in one
+// launch -- or `miss` when there is none or the baked-in lists are switched off.
+template <class Fn>
+int with_hot_list(const AggParams& p, int miss, Fn&& fn) {
+    if (!hot_lists_on()) return miss;
+#define DGN_HOT(NA, OPS, CHS, NS, SCS, N, S, A)                                                                  \
+    if (p.n_agg == NA && p.op_pack == OPS && p.ch_pack == CHS && p.n_scalers == NS && p.scaler_pack == SCS &&    \
+        p.agg_total == NA && p.agg_offset == 0 && p.n_ch == N) return fn(HotList<NA, OPS, CHS, NS, SCS, N, S, A>{});
+#include "dgn_agg_hot.hpp"
+#undef DGN_HOT
+    return miss;
+}
 
 // runtime (n_ch, stats, av) -> compile-time configuration
 template <int VEC, bool BWD>
 int launch_vec(const AggParams& p, unsigned tiles, hipStream_t stream) {
     const bool stats = (p.need & (NEED_SQ | NEED_MAX | NEED_MIN)) != 0;
     const bool av = p.any_av;
-    // hot aggregator lists of the reference's configs: kernels with the list baked in (dgn_agg_hot.hpp)
-    static const bool no_hot = getenv("DGN_NO_HOT") != nullptr;
-#define DGN_HOT(NA, OPS, CHS, NS, SCS, N, S, A)                                                                  \
-    if (!no_hot && p.n_agg == NA && p.op_pack == OPS && p.ch_pack == CHS && p.n_scalers == NS && p.scaler_pack == SCS && \
-        p.agg_total == NA && p.agg_offset == 0 && p.n_ch == N) {                                                 \
-        using O = StaticOps<NA, OPS, CHS, NS, SCS>;                                                              \
-        if (p.Fv != p.F) {      /* rows of an odd width (DgnMsg.f_valid): the two lists that meet them, 8-byte lanes */ \
-            if constexpr (VEC == 2 && odd_width_list(NA, OPS, CHS)) {                                            \
-                if constexpr (BWD) return launch_backward_cfg<Cfg<VEC, N, S, A, true>, O>(p, tiles, stream);     \
-                else return launch_forward_cfg<Cfg<VEC, N, S, A, true>, O>(p, tiles, stream);                    \
-            }                                                                                                    \
-            set_error("f_valid: no kernel for this aggregator list (dgn_agg_f_valid_supported)");               \
-            return DGN_ERR_INVALID;                                                                              \
-        }                                                                                                        \
-        if constexpr (BWD) return launch_backward_cfg<Cfg<VEC, N, S, A>, O>(p, tiles, stream);                   \
-        else return launch_forward_cfg<Cfg<VEC, N, S, A>, O>(p, tiles, stream);                                  \
-    }
-#include "dgn_agg_hot.hpp"
-#undef DGN_HOT
+    // hot aggregator lists of the reference's configs: kernels with the list baked in (1: not one of them)
+    const int hot = with_hot_list(p, 1, [&](auto h) {
+        using H = decltype(h);
+        if (p.Fv != p.F) {      // rows of an odd width (DgnMsg.f_valid): the two lists that meet them, 8-byte lanes
+            if constexpr (VEC == 2 && H::odd_width()) {
+                if constexpr (BWD) return launch_backward_cfg<Cfg<VEC, H::NCH, H::STATS, H::AV, true>, typename H::Ops>(p, tiles, stream);
+                else return launch_forward_cfg<Cfg<VEC, H::NCH, H::STATS, H::AV, true>, typename H::Ops>(p, tiles, stream);
+            }
+            return 1;           // (no such kernel: the error below)
+        }
+        if constexpr (BWD) return launch_backward_cfg<Cfg<VEC, H::NCH, H::STATS, H::AV>, typename H::Ops>(p, tiles, stream);
+        else return launch_forward_cfg<Cfg<VEC, H::NCH, H::STATS, H::AV>, typename H::Ops>(p, tiles, stream);
+    });
+    if (hot != 1) return hot;
     if (p.Fv != p.F) { set_error("f_valid: no kernel for this aggregator list (dgn_agg_f_valid_supported)"); return DGN_ERR_INVALID; }
 #define DGN_GO(N, S, A)                                                                              \
     if (p.n_ch == N && stats == S && av == A) {                                                      \
@@ -2194,14 +2249,7 @@ int launch_vec(const AggParams& p, unsigned tiles, hipStream_t stream) {
 
 // is the launch's (list, scalers, channels) one of the baked-in hot lists (launch_vec would pick a StaticOps kernel)?
 inline bool is_hot_list(const AggParams& p) {
-    static const bool no_hot = getenv("DGN_NO_HOT") != nullptr;
-    if (no_hot) return false;
-#define DGN_HOT(NA, OPS, CHS, NS, SCS, N, S, A)                                                                  \
-    if (p.n_agg == NA && p.op_pack == OPS && p.ch_pack == CHS && p.n_scalers == NS && p.scaler_pack == SCS && \
-        p.agg_total == NA && p.agg_offset == 0 && p.n_ch == N) return true;
-#include "dgn_agg_hot.hpp"
-#undef DGN_HOT
-    return false;
+    return with_hot_list(p, 0, [](auto) { return 1; }) != 0;
 }
 
 // defined in dgn_agg_v1.hip / _v2.hip / _v4.hip

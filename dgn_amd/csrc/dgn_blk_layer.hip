@@ -184,24 +184,13 @@ int fill(P& p, const DgnBlockLayer* L, const Dims& d, bool bwd, const char* fn) 
     // the aggregator list as the sweep's device code reads it (fill_params of dgn_agg.hip), scalers applied outside
     p.a.n_agg = d.A; p.a.agg_total = d.A; p.a.n_ch = d.n_ch; p.a.n_scalers = 1; p.a.n_towers = 1;
     p.a.avg_log = spec->avg_log; p.a.eps = spec->eps;
-    uint32_t need = 0;
     for (int a = 0; a < d.A; ++a) {
         const int op = spec->agg_op[a], c = spec->agg_ch[a];
-        const bool dir = op >= DGN_AGG_DIR_AV && op <= DGN_AGG_DIR_DX_NO_ABS;
-        if (dir && (c < 0 || c >= d.n_ch)) { set_error("%s: aggregator %d: channel %d outside 0..%d", fn, a, c, d.n_ch - 1); return DGN_ERR_INVALID; }
-        p.a.op_pack |= (uint64_t)op << (4 * a);
-        p.a.ch_pack |= (uint64_t)(dir ? c : 0) << (3 * a);
-        switch (op) {
-            case DGN_AGG_MAX: need |= NEED_MAX | NEED_RECOMP; break;
-            case DGN_AGG_MIN: need |= NEED_MIN | NEED_RECOMP; break;
-            case DGN_AGG_STD: case DGN_AGG_VAR: need |= NEED_SQ | NEED_RECOMP | NEED_M_EMIT; break;
-            case DGN_AGG_DIR_AV: p.a.any_av = true; break;
-            case DGN_AGG_DIR_DX: need |= NEED_XIN | NEED_RECOMP; break;
-            case DGN_AGG_DIR_DX_NO_ABS: need |= NEED_XIN; break;
-            default: break;
-        }
+        if (op >= DGN_AGG_DIR_AV && op <= DGN_AGG_DIR_DX_NO_ABS && (c < 0 || c >= d.n_ch)) { set_error("%s: aggregator %d: channel %d outside 0..%d", fn, a, c, d.n_ch - 1); return DGN_ERR_INVALID; }
     }
-    p.a.need = need;
+    // (the sweep's packer gives this route the bits it always had: dims_of() rejected DGN_AGG_X_IN, the one op whose bits the route
+    //  never set, and the weighted sum adds none)
+    pack_agg_list(p.a, spec);
     p.desc = L->blocks->desc; p.n_blocks = d.n_blocks;
     p.indptr = L->graph->indptr; p.src = L->graph->src; p.csc_ptr = L->graph->csc_ptr; p.csc_pos = L->graph->csc_pos;
     p.eig = L->eig; p.ld_eig = (int32_t)L->ld_eig; p.n_ch = d.n_ch;
@@ -273,20 +262,30 @@ int launch_block(const P& p, dim3 grid, int threads, hipStream_t stream) {
 
 // The aggregator lists of the reference's configs run kernels with the list baked in (their per-row epilogue and coefficient code is
 // a third of the generic one's instructions -- and this route is instruction-bound); anything else the generic kernels.
-// BLK_LIST(n_agg, op_pack, ch_pack, n_ch, stats, av, has_pre)
+// Of the table's rows this route bakes the (list, has_pre) pairs the reference's configs run here, not every row twice:
+template <class H>
+constexpr bool blk_baked(bool pre) {
+    constexpr int mean = DGN_AGG_MEAN, amax = DGN_AGG_MAX, amin = DGN_AGG_MIN, av = DGN_AGG_DIR_AV, dx = DGN_AGG_DIR_DX;
+    if (H::is(mean, amax, amin, av, dx)) return pre;         // ZINC towers / complex (BASELINE c2)
+    if (H::is(mean, amax, amin, dx, av)) return true;        // HIV / PCBA json: simple (BASELINE c4), complex / towers
+    if (H::is(mean, DGN_AGG_DIR_DX_NO_ABS)) return !pre;     // BASELINE c1 (simple)
+    if (H::is(mean, dx, dx)) return !pre && H::NCH == 2;     // dir1-dx dir2-dx: CIFAR10 json, simple (BASELINE c3)
+    if (H::is(mean, dx, av)) return pre;                     // ZINC json, complex
+    return false;
+}
+
+// (fill() leaves p.a with one scaler, agg_total = A and zeros elsewhere: the sweep's matcher applies to it as it is; 1 = not baked)
 template <bool FWD>
 int launch_for_list(const P& p, bool pre, dim3 grid, int threads, hipStream_t stream) {
-    static const bool no_hot = getenv("DGN_NO_HOT") != nullptr;
-#define BLK_LIST(NA, OPS, CHS, N, S_, A_, PRE_)                                                                              \
-    if (!no_hot && p.a.n_agg == NA && p.a.op_pack == OPS && p.a.ch_pack == CHS && p.n_ch == N && pre == PRE_)               \
-        return launch_block<FWD, StaticOps<NA, OPS, CHS, 1, 0x0u>, Cfg<1, N, S_, A_>, PRE_>(p, grid, threads, stream);
-    BLK_LIST(5, 0x86320ull, 0x0ull, 1, true, true, true)      // mean max min dir1-av dir1-dx: ZINC towers / complex (BASELINE c2)
-    BLK_LIST(5, 0x68320ull, 0x0ull, 1, true, true, false)     // mean max min dir1-dx dir1-av: HIV / PCBA json, simple (BASELINE c4)
-    BLK_LIST(5, 0x68320ull, 0x0ull, 1, true, true, true)      //   ... complex / towers
-    BLK_LIST(2, 0x90ull, 0x0ull, 1, false, false, false)      // mean dir1-dx-no-abs: BASELINE c1 (simple)
-    BLK_LIST(3, 0x880ull, 0x40ull, 2, false, false, false)    // mean dir1-dx dir2-dx: CIFAR10 json, simple (BASELINE c3)
-    BLK_LIST(3, 0x680ull, 0x0ull, 1, false, true, true)       // mean dir1-dx dir1-av: ZINC json, complex
-#undef BLK_LIST
+    const int rc = with_hot_list(p.a, 1, [&](auto h) {
+        using H = decltype(h);
+        if constexpr (blk_baked<H>(false))
+            if (!pre) return launch_block<FWD, typename H::Ops, Cfg<1, H::NCH, H::STATS, H::AV>, false>(p, grid, threads, stream);
+        if constexpr (blk_baked<H>(true))
+            if (pre) return launch_block<FWD, typename H::Ops, Cfg<1, H::NCH, H::STATS, H::AV>, true>(p, grid, threads, stream);
+        return 1;
+    });
+    if (rc != 1) return rc;
     if (pre) return launch_block<FWD, DynOps, Cfg<1, blk::kMaxCh, true, true>, true>(p, grid, threads, stream);
     return launch_block<FWD, DynOps, Cfg<1, blk::kMaxCh, true, true>, false>(p, grid, threads, stream);
 }

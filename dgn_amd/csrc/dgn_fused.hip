@@ -30,31 +30,19 @@ int launch_fwd(const FusedParams& p, size_t lds, hipStream_t st) {
 // (StaticOps) the sweep half stays under the 128 registers a 16-wave workgroup leaves per lane; the generic list decoder does not
 // (it spilled in every accumulator configuration).  Any other list runs sweep and posttrans as separate kernels.
 bool is_hot(const AggParams& a) {
-    static const bool no_hot = getenv("DGN_NO_HOT") != nullptr;
-    if (no_hot) return false;
-#define DGN_HOT(NA, OPS, CHS, NS, SCS, N, S, A)                                                                          \
-    if (a.n_agg == NA && a.op_pack == OPS && a.ch_pack == CHS && a.n_scalers == NS && a.scaler_pack == SCS && a.agg_total == NA && \
-        a.agg_offset == 0 && a.n_ch == N)                                                                                \
-        return NS == 1;
-#include "dgn_agg_hot.hpp"
-#undef DGN_HOT
-    return false;
+    return with_hot_list(a, 0, [](auto h) { return (int)(decltype(h)::NS == 1); }) != 0;
 }
 
 int dispatch_fwd(const FusedParams& p, size_t lds, hipStream_t st) {
-    const AggParams& a = p.a;
-#define DGN_HOT(NA, OPS, CHS, NS, SCS, N, S, A)                                                                          \
-    if (a.n_agg == NA && a.op_pack == OPS && a.ch_pack == CHS && a.n_scalers == NS && a.scaler_pack == SCS && a.agg_total == NA && \
-        a.agg_offset == 0 && a.n_ch == N) {                                                                              \
-        if constexpr (NS == 1) return launch_fwd<Cfg<2, N, S, A>, StaticOps<NA, OPS, CHS, NS, SCS>>(p, lds, st);         \
-        else return DGN_ERR_INVALID;          /* (scalers are folded behind posttrans: lists with in-sweep scalers never come here) */ \
-    }
-#include "dgn_agg_hot.hpp"
-#undef DGN_HOT
+    const int rc = with_hot_list(p.a, 1, [&](auto h) {
+        using H = decltype(h);
+        if constexpr (H::NS == 1) return launch_fwd<Cfg<2, H::NCH, H::STATS, H::AV>, typename H::Ops>(p, lds, st);
+        else return (int)DGN_ERR_INVALID;     // (scalers are folded behind posttrans: lists with in-sweep scalers never come here)
+    });
+    if (rc != 1) return rc;
     set_error("no fused kernel for this aggregator list");
     return DGN_ERR_INVALID;
 }
-
 
 bool al8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) == 0; }
 
@@ -74,11 +62,7 @@ extern "C" int dgn_layer_fused_supported(const DgnGraph* g, const DgnAggSpec* sp
     AggParams a{};
     a.n_towers = spec->n_towers; a.agg_total = a_total; a.Ft = Ft;
     a.n_agg = spec->n_agg; a.n_scalers = 1; a.n_ch = spec->n_ch; a.agg_offset = 0;
-    for (int i = 0; i < spec->n_agg; ++i) {
-        const int op = spec->agg_op[i];
-        a.op_pack |= (uint64_t)op << (4 * i);
-        a.ch_pack |= (uint64_t)((op >= DGN_AGG_DIR_AV && op <= DGN_AGG_DIR_DX_NO_ABS) ? spec->agg_ch[i] : 0) << (3 * i);
-    }
+    pack_agg_list(a, spec);      // (the single identity scaler checked above packs to zero)
     return is_hot(a) && fused_lds_floats(a, nq) * sizeof(float) <= 160 * 1024;
 }
 
