@@ -417,3 +417,103 @@ def rotate(eig: torch.Tensor, augmentation_deg: float, generator: Optional[torch
     out[:, 1] = cos * eig[:, 1] + sine * eig[:, 2]
     out[:, 2] = cos * eig[:, 2] - sine * eig[:, 1]
     return out
+
+
+# ---- the same augmentations as one kernel with a device-resident random stream (csrc/dgn_eig_augment.hip) -------------------------
+
+def _flip_mask(flip) -> int:
+    """``flip`` of ``EigAugment`` -> the kernel's column mask (bit j = column j): None -> 0, "all" -> every column, a column index, or a
+    sequence of column indices."""
+    if flip is None:
+        return 0
+    if isinstance(flip, str):
+        if flip != "all":
+            raise ValueError(f"EigAugment: flip must be None, 'all', a column index or a sequence of column indices, got '{flip}'")
+        return 0xFFFFFFFF
+    if isinstance(flip, bool):
+        raise TypeError("EigAugment: flip takes column indices, not a bool (flip='all' for the molecule loop's --flip, "
+                        "EigAugment.superpixels(augmentation, flip) for the superpixel loop's)")
+    cols = [flip] if isinstance(flip, int) else list(flip)
+    mask = 0
+    for c in cols:
+        if isinstance(c, bool) or not isinstance(c, int):
+            raise TypeError(f"EigAugment: a flip column must be an int, got {c!r}")
+        if not 0 <= c < 32:
+            raise ValueError(f"EigAugment: flip column {c} outside 0 .. 31")
+        mask |= 1 << c
+    return mask
+
+
+class EigAugment:
+    """The eigenvector augmentations of the reference's training loops as ONE kernel launch (``ops.eig_augment``) that draws from a random
+    stream kept on the device, so it can sit inside a captured step (``hipgraph.Captured*Step(..., augment=...)``) and draw new values on
+    every replay:
+
+    * ``EigAugment.molecules()``: a random sign per ENTRY of ``eig`` (train/train_molecules_graph_regression.py:29-33, ``--flip``);
+    * ``EigAugment.superpixels(augmentation, flip)``: a random per-node rotation of the (eig1, eig2) pair by up to ``augmentation`` degrees,
+      then a random sign per node on column 2 (train/train_superpixels_graph_classification.py:29-42).
+
+    ``rotate_deg``: the largest angle, 0 = no rotation (the reference's ``sqrt(1 - sin^2)`` form: it differs from a rotation beyond 90
+    degrees, as there); ``flip``: None, ``"all"``, a column index or a sequence of column indices.  The object owns the stream, a device int64
+    ``[4]`` tensor ``state = {key, calls, ticket, 0}``: the key is drawn ONCE from torch's generator of the device at construction (so
+    ``torch.manual_seed`` before it fixes the run) or taken from ``seed``, and every call -- eager or replayed -- advances ``calls`` by one on
+    the device.  Row i of call c draws Philox4x32-10(counter (i, c), key): ``get_state()`` / ``set_state(key, calls)`` are what a checkpoint
+    stores to resume with the values the uninterrupted run would have drawn.  Constructing one inside a stream capture raises (the key would
+    be drawn by a captured launch into the capture's private pool: every replay the same key).
+
+    ``aug(eig)`` returns a new tensor; ``aug(eig, out=buf)`` writes ``buf`` (``eig`` itself is allowed) and bumps its version counter, so a
+    ``DGNGraph`` that cached edge weights for ``buf`` computes them again.
+
+    Not covered: the superpixel loop's ``--distortion`` (its line 48 adds the whole ``[N, K]`` tensor to a column and raises in the reference;
+    ``dgn_amd.eig.distort`` ships the evident intent, and that needs a batch-wide mean of |column| -- a reduction, not a per-row kernel)."""
+
+    def __init__(self, rotate_deg: float = 0.0, flip=None, device=None, seed: Optional[int] = None):
+        self.rotate_deg = float(rotate_deg)
+        if not math.isfinite(self.rotate_deg):
+            raise ValueError(f"EigAugment: rotate_deg must be finite, got {rotate_deg}")
+        self.flip_mask = _flip_mask(flip)
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 63):
+            raise ValueError(f"EigAugment: seed must be an int in [0, 2^63), got {seed!r}")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.DgnError("EigAugment: CUDA devices only (dgn_amd has no CPU path)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("EigAugment: construct it outside a stream capture (its state would live in the capture's private pool and "
+                               "its key be drawn by a captured launch: every replay the same key)")
+        self.device = dev
+        self.state = torch.zeros(4, dtype=torch.int64, device=dev)
+        if seed is None:
+            self.state[:1] = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev)
+        else:
+            self.state[0] = seed
+
+    @classmethod
+    def molecules(cls, **kw) -> "EigAugment":
+        """``--flip`` of the molecule loop: a random sign per entry."""
+        return cls(rotate_deg=0.0, flip="all", **kw)
+
+    @classmethod
+    def superpixels(cls, augmentation: float = 0.0, flip: bool = False, **kw) -> "EigAugment":
+        """``--augmentation`` / ``--flip`` of the superpixel loop: the rotation (off at or below 1e-7 degrees, as there), then the sign of column 2."""
+        return cls(rotate_deg=float(augmentation) if augmentation > 1e-7 else 0.0, flip=2 if flip else None, **kw)
+
+    def __call__(self, eig: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        from .ops import eig_augment
+        return eig_augment(eig, self.state, self.rotate_deg, self.flip_mask, out=out)
+
+    def get_state(self):
+        """``(key, calls so far)`` as Python ints (one read-back)."""
+        key, calls = self.state[:2].tolist()
+        return key, calls
+
+    def set_state(self, key: int, calls: int = 0) -> None:
+        """Continue from ``(key, calls)``: what ``get_state`` returned (a checkpoint), or a chosen point of the stream."""
+        key, calls = int(key), int(calls)
+        if not (-2 ** 63 <= key < 2 ** 63 and 0 <= calls < 2 ** 63):
+            raise ValueError("EigAugment.set_state: key and calls must fit an int64, calls >= 0")
+        self.state.copy_(torch.tensor([key, calls, 0, 0], dtype=torch.int64))
+
+    def __repr__(self):
+        return f"EigAugment(rotate_deg={self.rotate_deg}, flip_mask={self.flip_mask:#x}, device='{self.device}')"

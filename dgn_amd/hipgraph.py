@@ -17,9 +17,12 @@ recomputed inside the captured region) and the cotangent rows of the padding mus
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, Optional, Tuple
+from typing import TYPE_CHECKING, Callable, Dict, Optional, Tuple
 
 import torch
+
+if TYPE_CHECKING:
+    from .eig import EigAugment
 
 
 def capture(step: Callable[[], None], warmup: int = 3) -> torch.cuda.CUDAGraph:
@@ -119,7 +122,7 @@ class _CapturedStep:
 
     _REFUSED = ()      # (test of the net, the ValueError's text) pairs, in the order they are checked
 
-    def __init__(self, net, n_cap: int, e_cap: int, eig_dim: int, device=None):
+    def __init__(self, net, n_cap: int, e_cap: int, eig_dim: int, device=None, augment: Optional["EigAugment"] = None):
         dev = torch.device(device if device is not None else next(net.parameters()).device)
         for refused, why in self._REFUSED:
             if refused(net):
@@ -127,6 +130,19 @@ class _CapturedStep:
         self.net, self.device = net, dev
         self.pb = PaddedBatch(n_cap, e_cap, dev, eig_dim)
         self.snorm = self.pb.add_node_tensor("snorm", 1)
+        # eigenvector augmentation (``dgn_amd.EigAugment``): the loads write the batch's eig into ``eig_src`` and the step's first launch
+        # draws the augmented ``ndata['eig']`` from it -- new values on every replay; ``pos_enc`` stays as loaded, as in the reference's loops
+        self.augment, self.eig_src = augment, None
+        if augment is not None:
+            from .eig import EigAugment
+            if not isinstance(augment, EigAugment):
+                raise TypeError(f"{type(self).__name__}: augment must be a dgn_amd.EigAugment, got {type(augment).__name__}")
+            if not 1 <= eig_dim <= 32 or (augment.rotate_deg != 0 and eig_dim < 3):
+                raise ValueError(f"{type(self).__name__}: augment takes 1 <= eig_dim <= 32, and >= 3 with a rotation (it turns columns 1 and 2); "
+                                 f"eig_dim = {eig_dim}")
+            if augment.device != self.pb.graph.ndata["eig"].device:
+                raise ValueError(f"{type(self).__name__}: the EigAugment lives on {augment.device}, the step on {self.pb.graph.ndata['eig'].device}")
+            self.eig_src = torch.zeros(n_cap, eig_dim, dtype=torch.float32, device=dev)
         # positional encodings: a static [n_cap, K] buffer the net reads from the graph's ndata (rows behind the batch stay zero)
         self.pos_enc_dim = int(getattr(net, "pos_enc_dim", 0) or 0)
         if self.pos_enc_dim > 0:
@@ -144,6 +160,22 @@ class _CapturedStep:
         if pos_enc.dim() != 2 or pos_enc.shape[1] != self.pos_enc_dim:
             raise ValueError(f"{who}.load: pos_enc must be [num_nodes, {self.pos_enc_dim}], got {tuple(pos_enc.shape)}")
         return {"snorm": snorm, "pos_enc": pos_enc}
+
+    def _load_eig(self, eig, num_nodes: int):
+        """The ``eig`` argument of ``PaddedBatch.load``: the batch's own without an ``augment``; with one the batch's eig goes to ``eig_src``
+        (zero behind the batch) and the graph's buffer is left to the step's first launch."""
+        if self.augment is None:
+            return eig
+        num_nodes = int(num_nodes)
+        self.eig_src[:num_nodes].copy_(eig, non_blocking=True)
+        self.eig_src[num_nodes:].zero_()
+        return None
+
+    def _augment(self) -> None:
+        """The first launch of a step with an ``augment``: ``ndata['eig']`` drawn from ``eig_src`` (the reference's loops replace
+        ``batch_graphs.ndata['eig']`` ahead of ``model.forward``; the layers and the directional readouts read it from there)."""
+        if self.augment is not None:
+            self.augment(self.eig_src, out=self.pb.graph.ndata["eig"])
 
     def _set_optimizer(self, optimizer, lr: float) -> None:
         """The last act of a constructor (a refused construction leaves the net's Parameter objects alone)."""
@@ -198,12 +230,13 @@ class CapturedNetStep(_CapturedStep):
                                  "buffer); run them eagerly or build the net with edge_feat=False"),)
 
     def __init__(self, net, n_cap: int, e_cap: int, g_cap: int, eig_dim: int, lr: float = 1e-3, optimizer=None, device=None,
-                 max_graph_nodes: Optional[int] = None, max_graph_edges: Optional[int] = None):
+                 max_graph_nodes: Optional[int] = None, max_graph_edges: Optional[int] = None, augment: Optional["EigAugment"] = None):
         """``max_graph_nodes`` / ``max_graph_edges``: the largest graph (nodes, directed edges) of the dataset.  Given both, the padded graph
         gets a static block table (``DGNGraph.set_block_capacity``) and the captured step runs its layers on the graph-block route -- five
-        launches per layer and step instead of ~28."""
+        launches per layer and step instead of ~28.  ``augment``: a ``dgn_amd.EigAugment`` -- every step (and every replay) then starts by drawing a
+        newly augmented ``eig`` from the loaded batch's, as the reference's loops do with ``--flip`` / ``--augmentation``: one more launch."""
         from .graph import DGNGraph
-        super().__init__(net, n_cap, e_cap, eig_dim, device)
+        super().__init__(net, n_cap, e_cap, eig_dim, device, augment=augment)
         dev = self.device
         # graph rows of the readout: g_cap - 1 real graphs at most, then PAD_ROWS rows that share the padding nodes (ONE padding row was a
         # single wave walking ~10 % of the batch's nodes in sequence: 40 us per direction of a 0.77 ms step)
@@ -246,7 +279,7 @@ class CapturedNetStep(_CapturedStep):
         sizes = torch.as_tensor(sizes, dtype=torch.int64)
         G = sizes.numel()
         self._check_graph_rows(G, num_nodes)
-        self.pb.load(src, dst, num_nodes, eig, node=node, graph_sizes=sizes)
+        self.pb.load(src, dst, num_nodes, self._load_eig(eig, num_nodes), node=node, graph_sizes=sizes)
         self.atoms[:num_nodes].copy_(atoms, non_blocking=True)
         self.atoms[num_nodes:].zero_()
         self._load_readout(sizes, num_nodes)
@@ -290,10 +323,13 @@ class CapturedNetStep(_CapturedStep):
         node = {"feat": self.atoms}
         if self.pos_enc_dim > 0:
             node["pos_enc"] = self.pb.node["pos_enc"]
+        if self.augment is not None:
+            node["eig"] = self.eig_src
         self.pb.graph.load_packed(ds, p, node=node, graph={"label": self.targets}, g_rows_out=self.g_rows, snorm_n=self.snorm)
         self._load_readout(torch.from_numpy(p.sizes), p.N)
 
     def _step(self) -> None:
+        self._augment()
         self.opt.zero_grad(set_to_none=True)
         self.pb.graph.invalidate_caches()
         scores = self.net(self.pb.graph, self.atoms, None, self.snorm, None)
@@ -396,8 +432,9 @@ class CapturedNodeStep(_CapturedStep):
 
     _REFUSED = ((_HAS_EDGE_FEAT, "CapturedNodeStep: nets with edge_feat=True are not supported (no static edge-feature buffer)"),)
 
-    def __init__(self, net, n_cap: int, e_cap: int, eig_dim: int, lr: float = 1e-3, optimizer=None, device=None):
-        super().__init__(net, n_cap, e_cap, eig_dim, device)
+    def __init__(self, net, n_cap: int, e_cap: int, eig_dim: int, lr: float = 1e-3, optimizer=None, device=None, augment: Optional["EigAugment"] = None):
+        """``augment``: as for ``CapturedNetStep``."""
+        super().__init__(net, n_cap, e_cap, eig_dim, device, augment=augment)
         dev = self.device
         self.n_classes = int(net.n_classes)
         self.feats = torch.zeros(n_cap, dtype=torch.int64, device=dev)
@@ -410,7 +447,7 @@ class CapturedNodeStep(_CapturedStep):
         """feats [num_nodes] int64 node types, labels [num_nodes] int64 classes; sizes: nodes per graph (only for a graph with a block table);
         pos_enc [num_nodes, pos_enc_dim] (any strides) for a net with positional encodings, None for every other."""
         num_nodes = int(num_nodes)
-        self.pb.load(src, dst, num_nodes, eig, node=self._node_tensors(snorm, pos_enc, "CapturedNodeStep"), graph_sizes=sizes)
+        self.pb.load(src, dst, num_nodes, self._load_eig(eig, num_nodes), node=self._node_tensors(snorm, pos_enc, "CapturedNodeStep"), graph_sizes=sizes)
         self.feats[:num_nodes].copy_(feats, non_blocking=True)
         self.feats[num_nodes:].zero_()
         self.labels[:num_nodes].copy_(labels, non_blocking=True)
@@ -425,9 +462,12 @@ class CapturedNodeStep(_CapturedStep):
         node = {"feat": self.feats, "label": self.labels}
         if self.pos_enc_dim > 0:
             node["pos_enc"] = self.pb.node["pos_enc"]
+        if self.augment is not None:
+            node["eig"] = self.eig_src
         self.pb.graph.load_packed(ds, ids, node=node, snorm_n=self.snorm)
 
     def _step(self) -> None:
+        self._augment()
         self.opt.zero_grad(set_to_none=True)
         self.pb.graph.invalidate_caches()
         scores = self.net(self.pb.graph, self.feats, None, self.snorm, None)

@@ -2355,3 +2355,45 @@ def mlp_head(x: torch.Tensor, weights, biases) -> torch.Tensor:
         raise ValueError(f"mlp_head: float32 x [N, in] with unit column stride and 1 to 4 chained weights of widths 1 .. 128 (at most 20480 "
                          f"elements) required (mlp_head_supported), got x {x.dtype} {tuple(x.shape)} and weights {[tuple(w.shape) for w in weights]}")
     return _MLPHead.apply(x, len(weights), *weights, *biases)
+
+
+def eig_augment(eig: torch.Tensor, state: torch.Tensor, rotate_deg: float = 0.0, flip_mask: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The eigenvector augmentations of the reference's training loops as ONE launch (``dgn_eig_augment`` of the C ABI): the random sign per
+    entry of train/train_molecules_graph_regression.py:29-33 (``flip_mask = (1 << K) - 1``), and the per-node rotation of the (eig1, eig2)
+    pair by up to ``rotate_deg`` degrees followed by the random sign on column 2 of train/train_superpixels_graph_classification.py:29-42
+    (``flip_mask = 1 << 2``).  ``eig``: CUDA fp32 ``[N, K]``, ``1 <= K <= 32``, unit column stride and any row stride (a ``[:, :K]`` view is
+    fine); ``state``: the device int64 ``[4]`` stream ``{key, calls, ticket, 0}`` the kernel itself advances by one call (``dgn_amd.EigAugment``
+    owns one); ``flip_mask``: bit j = column j, bits from K on are ignored.  Returns a new contiguous tensor, or ``out`` (same shape; may be
+    ``eig`` itself), whose version counter is bumped: the graph's edge-weight cache keys on it.  No host read-back: capturable, and every
+    replay of the capture draws new values."""
+    if not eig.is_cuda or not state.is_cuda:
+        raise _lib.DgnError("eig_augment: CUDA tensors only (dgn_amd has no CPU path)")
+    if eig.dtype != torch.float32 or eig.dim() != 2 or (eig.shape[1] > 1 and eig.stride(1) != 1):
+        raise ValueError(f"eig_augment: eig must be a float32 [N, K] tensor with unit column stride, got {eig.dtype} {tuple(eig.shape)} strides {eig.stride()}")
+    N, K = eig.shape
+    if not 1 <= K <= 32:
+        raise ValueError(f"eig_augment: 1 <= K <= 32 columns required, got {K}")
+    if state.dtype != torch.int64 or tuple(state.shape) != (4,) or not state.is_contiguous() or state.device != eig.device:
+        raise ValueError("eig_augment: state must be a contiguous int64 [4] tensor on eig's device")
+    flip_mask = int(flip_mask)
+    if not 0 <= flip_mask < 2 ** 32:
+        raise ValueError(f"eig_augment: flip_mask is a 32-bit column mask, got {flip_mask}")
+    if rotate_deg != 0 and K < 3:
+        raise ValueError(f"eig_augment: the rotation turns columns 1 and 2, eig has {K}")
+    if out is None:
+        res = torch.empty(N, K, dtype=torch.float32, device=eig.device)
+    else:
+        if out.dtype != torch.float32 or out.shape != eig.shape or out.device != eig.device or (K > 1 and out.stride(1) != 1):
+            raise ValueError(f"eig_augment: out must be a float32 {tuple(eig.shape)} tensor with unit column stride on eig's device")
+        if N > 1 and out.stride(0) < K:
+            raise ValueError("eig_augment: the rows of out overlap")
+        res = out
+    ld = lambda t: t.stride(0) if N > 1 else K
+    if N > 1 and ld(eig) < K:
+        raise ValueError("eig_augment: the rows of eig overlap")
+    rc = _lib.load().dgn_eig_augment(N, K, eig.data_ptr(), ld(eig), res.data_ptr(), ld(res), float(rotate_deg),
+                                     flip_mask - (1 << 32) if flip_mask >= 1 << 31 else flip_mask, state.data_ptr(), _lib.stream_ptr(eig.device))
+    _lib.check(rc, "dgn_eig_augment")
+    if out is not None:
+        torch.autograd.graph.increment_version(out)      # (a ctypes launch is invisible to torch: DGNGraph caches by (tensor, version))
+    return res

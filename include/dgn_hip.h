@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DGN_ABI_VERSION 37
+#define DGN_ABI_VERSION 38
 
 #define DGN_MAX_AGG 16     /* aggregators per launch (the host splits longer lists)            */
 #define DGN_MAX_CH 4       /* edge-weight channels per launch                                   */
@@ -1098,6 +1098,27 @@ typedef struct DgnCollate {
     int64_t* n_valid;
 } DgnCollate;
 int dgn_collate(const DgnCollate* c, void* stream);
+
+/* ---- eigenvector augmentations of the training loops (dgn_eig_augment.hip) ------------------------------------------------------
+ * The reference augments the Laplacian eigenvectors of every batch before the forward pass: a random sign per entry of `eig` in the
+ * molecule loop (train/train_molecules_graph_regression.py:29-33, --flip), and in the superpixel loop a random per-node rotation of
+ * the (eig1, eig2) pair by up to --augmentation degrees, then a random sign per node on column 2
+ * (train/train_superpixels_graph_classification.py:29-42).  Here both are ONE kernel, one thread per row, whose random stream is kept
+ * and advanced on the device by the kernel itself: nothing else is launched, so a captured graph draws new values on every replay.
+ *   eig / out    fp32 [n_rows, K] with row strides ld_in / ld_out >= K, 1 <= K <= 32; out == eig with equal strides is allowed (a
+ *                thread reads its whole row before it writes)
+ *   state        DEVICE int64 [4] = {key, calls, ticket, 0}, ticket = 0 between calls.  Row i of call number c = calls draws
+ *                r[0..3] = Philox4x32-10(counter = (lo32 i, hi32 i, lo32 c, hi32 c), key = (lo32 key, hi32 key)); the call that
+ *                finishes leaves calls = c + 1: the same (key, calls) gives the same output for any grid
+ *   rotate_deg   != 0 (needs K >= 3): u = (r[0] >> 8) 2^-24, angle = (u - 0.5) 2 rotate_deg, s = sin(angle pi / 180),
+ *                c = sqrt(1 - s^2) -- the reference's form, |cos| beyond +-90 degrees --, out1 = c x1 + s x2, out2 = c x2 - s x1
+ *   flip_mask    after the rotation, as in the superpixel loop: column j < K with bit j set is multiplied (0 -> -0, as torch.mul) by
+ *                +1 where bit j of r[1] is set, by -1 where not.  Molecule loop: flip_mask = (1 << K) - 1, rotate_deg = 0;
+ *                superpixel loop: flip_mask = 1 << 2 plus its angle.  Columns not named are copied.
+ * n_rows == 0: DGN_OK, nothing launched, state untouched.  K outside 1..32, a rotation with K < 3, strides below K, a non-finite
+ * angle: DGN_ERR_INVALID, nothing launched. */
+int dgn_eig_augment(int64_t n_rows, int32_t K, const float* eig, int64_t ld_in, float* out, int64_t ld_out, float rotate_deg,
+                    int32_t flip_mask, int64_t* state, void* stream);
 
 #ifdef __cplusplus
 }
