@@ -53,7 +53,8 @@ int validate(const DgnGraph* g, const DgnAggSpec* spec, const DgnMsg* msg, const
     if (spec->n_ch < 0 || spec->n_ch > DGN_MAX_CH) { set_error("n_ch=%d outside 0..%d", spec->n_ch, DGN_MAX_CH); return DGN_ERR_INVALID; }
     if (spec->n_scalers < 1 || spec->n_scalers > DGN_MAX_SCALERS) { set_error("n_scalers=%d outside 1..%d", spec->n_scalers, DGN_MAX_SCALERS); return DGN_ERR_INVALID; }
     if (spec->n_towers < 1 || msg->F < 1 || msg->F % spec->n_towers != 0) { set_error("F=%lld not divisible by n_towers=%d", (long long)msg->F, spec->n_towers); return DGN_ERR_INVALID; }
-    if (!msg->x_src && !msg->x_dst && !msg->m_edge) { set_error("message has no term"); return DGN_ERR_INVALID; }
+    // (x_dst alone would be the same message in every slot of a row -- and the gather loops read their one gathered part unconditionally)
+    if (!msg->x_src && !msg->m_edge) { set_error("a message needs a gathered term: x_src or m_edge (x_dst alone is the same in every slot)"); return DGN_ERR_INVALID; }
     if (msg->f_valid != 0 && (msg->f_valid != msg->F - 1 || (msg->F & 1) || msg->F < 4 || !msg->x_src || msg->x_dst || msg->m_edge || spec->n_towers != 1 ||
                               msg->ld_src < msg->f_valid || (msg->x_in && msg->ld_in < msg->f_valid) || g->n_hub > 0 || !dgn_agg_f_valid_supported(spec))) {
         set_error("f_valid = %d: rows of an odd width need F = f_valid + 1 even, x_src (and x_in) alone, one tower, no hub rows, a list of dgn_agg_f_valid_supported()", msg->f_valid); return DGN_ERR_INVALID;

@@ -160,7 +160,8 @@ typedef struct DgnAggSpec {
 } DgnAggSpec;
 
 /* The message of CSR slot j into node i is  m_j = x_src[src_j] + x_dst[i] + m_edge[j];
- * any of the three terms may be NULL (at least one must be given).
+ * any of the three terms may be NULL, but one of the two GATHERED terms, x_src or m_edge, must be given: x_dst alone (the
+ * same message in every slot of a row) is refused with DGN_ERR_INVALID.
  *   simple layer:            x_src = h                                   (dgn_layer.py:154-155)
  *   complex/towers, 1-layer pretrans:  x_src = h W_s^T, x_dst = h W_d^T + b (+ m_edge = ef W_e^T)
  *   any other pretrans:      m_edge = materialised messages in CSR slot order

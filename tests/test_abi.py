@@ -250,6 +250,43 @@ def test_argument_validation_runs_before_any_device_work(lib):
     assert lib.dgn_scale_combine_backward_workspace_bytes(1000, 5, 14) > 0
 
 
+def test_message_of_x_dst_alone_is_refused_before_any_launch(lib):
+    """m_j = x_dst[i] for every slot j is no message (and the gather loops read their one gathered term unconditionally): the forward and
+    the backward return DGN_ERR_INVALID from the host-side checks -- nothing launched, `out` and the sinks left as they were.  Host memory
+    stands in for the device's: nothing may read or write it."""
+    import numpy as np
+    from dgn_amd import _lib
+    err = lambda: lib.dgn_last_error().decode()
+    N, F_ = 3, 4
+    indptr, src = np.array([0, 1, 2, 3], dtype=np.int32), np.array([1, 2, 0], dtype=np.int32)
+    x = np.arange(N * F_, dtype=np.float32).reshape(N, F_)
+    out, g_out = np.full((N, F_), 7.0, dtype=np.float32), np.ones((N, F_), dtype=np.float32)
+    sinks = [np.full((N, F_), 9.0, dtype=np.float32) for _ in range(3)]
+    ptr = lambda a: a.ctypes.data
+    g = _lib.DgnGraph()
+    g.n_nodes, g.n_edges, g.indptr, g.src = N, 3, ptr(indptr), ptr(src)
+    spec = _lib.DgnAggSpec()
+    spec.n_agg, spec.n_scalers, spec.n_towers, spec.eps = 1, 1, 1, 1e-8            # mean | identity
+    msg = _lib.DgnMsg()
+    msg.F, msg.x_dst, msg.ld_dst, msg.x_in, msg.ld_in = F_, ptr(x), F_, ptr(x), F_
+    gr = _lib.DgnMsgGrad()
+    gr.g_src, gr.ld_src, gr.g_dst, gr.ld_dst, gr.g_in, gr.ld_in = ptr(sinks[0]), F_, ptr(sinks[1]), F_, ptr(sinks[2]), F_
+    args = (C.byref(g), C.byref(spec), C.byref(msg), None, 0, None)
+    for accumulate in (0, 1):
+        gr.accumulate = accumulate
+        for rc in (lib.dgn_agg_forward(*args, ptr(out), F_, None, 0, None),
+                   lib.dgn_agg_forward_aux(*args, ptr(out), F_, None, None, 0, None),
+                   lib.dgn_agg_backward(*args, ptr(g_out), F_, C.byref(gr), None, 0, None),
+                   lib.dgn_agg_backward_aux(*args, ptr(g_out), F_, None, C.byref(gr), None, 0, None)):
+            assert rc == _lib.DGN_ERR_INVALID and "gathered term" in err(), (rc, err())
+    g.n_nodes, g.n_edges = 0, 0                                                    # ... also where there is nothing to do
+    assert lib.dgn_agg_forward(*args, ptr(out), F_, None, 0, None) == _lib.DGN_ERR_INVALID
+    assert lib.dgn_agg_backward(*args, ptr(g_out), F_, C.byref(gr), None, 0, None) == _lib.DGN_ERR_INVALID
+    assert (out == 7.0).all() and all((s == 9.0).all() for s in sinks)
+    msg.x_dst = None                                                               # (no term at all: the same refusal)
+    assert lib.dgn_agg_forward(*args, ptr(out), F_, None, 0, None) == _lib.DGN_ERR_INVALID and "gathered term" in err()
+
+
 def test_linear_entry_points_validate_before_any_device_work(lib):
     """dgn_linear_*: width limits, dense-row and alignment requirements, workspace size -- all host-side checks."""
     err = lambda: lib.dgn_last_error().decode()
