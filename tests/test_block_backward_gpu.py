@@ -19,18 +19,7 @@ def _dev():
     return torch.device("cuda")
 
 
-def _cuts_numpy(src, dst, N):
-    diff = np.zeros(N + 2, dtype=np.int64)
-    a, b = np.minimum(src, dst), np.maximum(src, dst)
-    m = a < b
-    np.add.at(diff, a[m] + 1, 1)
-    np.add.at(diff, b[m] + 1, -1)
-    cross = np.cumsum(diff)[: N + 1]
-    closed = cross == 0
-    last = np.maximum.accumulate(np.where(closed, np.arange(N + 1), 0))
-    cuts = np.flatnonzero(closed)
-    gap = int(np.diff(cuts).max()) if cuts.size > 1 else 0
-    return last, gap
+from agg_blk_graphs import closed_cuts as _cuts_numpy      # (the numpy restatement of dgn_graph_build_cuts)
 
 
 @pytest.mark.parametrize("kind", ["molecules", "chain_across", "isolated"])
