@@ -114,30 +114,43 @@ void fill_params(AggParams& p, const DgnGraph* g, const DgnAggSpec* spec, const 
     p.n_coef = n_coef_for(spec);
 }
 
-size_t hub_ws_bytes(const DgnGraph* g, const DgnAggSpec* spec, int64_t F) {
-    if (!g || g->n_hub <= 0) return 0;
-    size_t part = (size_t)g->n_chunks * n_slots_for(spec) * F * sizeof(float);
-    size_t sw = (size_t)g->n_chunks * DGN_MAX_CH * sizeof(float);
-    size_t coef = (size_t)g->n_hub * n_coef_for(spec) * F * sizeof(float);
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return up(part) + up(sw) + up(coef);
+// columns of an output / upstream-gradient row
+int64_t out_width(const DgnAggSpec* spec, int64_t F) {
+    return (int64_t)spec->n_scalers * (spec->agg_total > 0 ? spec->agg_total : spec->n_agg) * (spec->tower_stride > 0 ? F / spec->n_towers : F);
 }
 
-void carve_ws(AggParams& p, const DgnGraph* g, const DgnAggSpec* spec, void* ws) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    char* base = static_cast<char*>(ws);
-    size_t part = (size_t)g->n_chunks * n_slots_for(spec) * p.F * sizeof(float);
-    size_t sw = (size_t)g->n_chunks * DGN_MAX_CH * sizeof(float);
-    p.part = reinterpret_cast<float*>(base);
-    p.part_sw = reinterpret_cast<float*>(base + up(part));
-    p.coef = reinterpret_cast<float*>(base + up(part) + up(sw));
+constexpr int kTabBlocks = 512;      // workgroups of edge_table_grad_partial: one [K][F] partial table each
+size_t tab_part_bytes(int64_t F, int32_t K) { return K > 0 ? (size_t)kTabBlocks * K * F * sizeof(float) : 0; }
+
+// The workspace of a sweep: the hub rows' chunk partials (graphs with hub rows only); behind them, in the backward, the [E, F] staging
+// buffer of the two-phase scatter (`stage`) and the partial tables of the edge-type table's gradient (`n_edge_types` > 0).  `hub` =
+// the three hub parts, `scatter` = what the two-phase scatter needs, `total` = everything asked for.
+struct AggWs { WsSpan part, part_sw, coef, stage, tab_part; size_t hub, scatter, total; };
+AggWs agg_ws(const DgnGraph* g, const DgnAggSpec* spec, int64_t F, bool stage, int32_t n_edge_types) {
+    WsLayout L;
+    AggWs s{};
+    if (g->n_hub > 0) {
+        s.part = L.take((size_t)g->n_chunks * n_slots_for(spec) * F * sizeof(float));
+        s.part_sw = L.take((size_t)g->n_chunks * DGN_MAX_CH * sizeof(float));
+        s.coef = L.take((size_t)g->n_hub * n_coef_for(spec) * F * sizeof(float));
+    }
+    s.hub = L.total;
+    s.stage = L.take(stage ? (size_t)g->n_edges * F * sizeof(float) : 0);
+    s.scatter = L.total;
+    s.tab_part = L.take(tab_part_bytes(F, n_edge_types));
+    s.total = L.total;
+    return s;
+}
+void carve_hub(AggParams& p, const AggWs& s, void* ws) {
+    p.part = s.part.in<float>(ws);
+    p.part_sw = s.part_sw.in<float>(ws);
+    p.coef = s.coef.in<float>(ws);
 }
 
 // ---- gradient of the edge-type table: rows of the staged per-edge gradients summed by type -------------------------------
 // (the sweep parked d m_j of slot j at stage[csc_pos[j]]; d table[k] = sum of the rows whose slot has type k).  Two passes, fixed
 // slot ranges per wave and a fixed summation order: deterministic.
-constexpr int kTabBlocks = 512;
-constexpr int kTabGroup = 8;         // staged rows in flight per wave
+constexpr int kTabGroup = 8;        // staged rows in flight per wave
 
 __global__ __launch_bounds__(1024) void edge_table_grad_partial(const float* __restrict__ stage, const int32_t* __restrict__ csc_pos,
                                                                const int32_t* __restrict__ edge_type, int64_t n_edges, int F, int K,
@@ -194,8 +207,6 @@ __global__ __launch_bounds__(256) void edge_table_grad_final(const float* __rest
     }
 }
 
-size_t edge_table_ws_bytes(int64_t F, int32_t K) { return (((size_t)kTabBlocks * K * F * sizeof(float)) + 255) & ~(size_t)255; }
-
 int launch(int vec, const AggParams& p, unsigned tiles, hipStream_t stream, bool backward) {
     switch (vec) {
         case 4: return launch_agg_v4(p, tiles, stream, backward);
@@ -220,10 +231,8 @@ using namespace dgn;
 
 extern "C" size_t dgn_agg_workspace_bytes(const DgnGraph* g, const DgnAggSpec* spec, int64_t F) {
     if (!g || !spec) return 0;
-    return hub_ws_bytes(g, spec, F);
+    return agg_ws(g, spec, F, false, 0).total;
 }
-
-size_t stage_bytes(const DgnGraph* g, int64_t F) { return ((size_t)g->n_edges * F * sizeof(float) + 255) & ~(size_t)255; }
 
 // The aux byte table (AggParams.aux) applies when the 4-rows-per-wave kernels run a baked-in list that recomputes (max / min / dx)
 // but needs no message value in the emit pass (no std / var), with at most two weight channels: short-row graph, even width.
@@ -252,18 +261,17 @@ extern "C" size_t dgn_agg_aux_bytes(const DgnGraph* g, const DgnAggSpec* spec, c
     if (!g || !spec || !msg || msg->F <= 0 || spec->n_agg < 1 || spec->n_agg > DGN_MAX_AGG || spec->n_towers < 1) return 0;
     AggParams p;
     fill_params(p, g, spec, msg, nullptr, 0, nullptr);
-    return agg_aux_supported(p, msg) ? (((size_t)((g->n_nodes + 3) / 4) * 4 * msg->F + 255) & ~(size_t)255) : 0;     // (groups of four rows)
+    return agg_aux_supported(p, msg) ? up256((size_t)((g->n_nodes + 3) / 4) * 4 * msg->F) : 0;     // (groups of four rows)
 }
 
+// (what the caller adds to dgn_agg_backward_workspace_bytes() for a message with an edge-type table: the last span of the layout)
 extern "C" size_t dgn_agg_edge_table_workspace_bytes(int64_t F, int32_t n_edge_types) {
-    return (F > 0 && n_edge_types > 0) ? edge_table_ws_bytes(F, n_edge_types) : 0;
+    return F > 0 ? WsLayout{}.take(tab_part_bytes(F, n_edge_types)).bytes : 0;
 }
 
 extern "C" size_t dgn_agg_backward_workspace_bytes(const DgnGraph* g, const DgnAggSpec* spec, int64_t F, int32_t deterministic) {
     if (!g || !spec) return 0;
-    size_t n = hub_ws_bytes(g, spec, F);
-    if (deterministic && g->csc_ptr && g->csc_pos && g->n_edges > 0) n += stage_bytes(g, F);
-    return n;
+    return agg_ws(g, spec, F, deterministic && g->csc_ptr && g->csc_pos && g->n_edges > 0, 0).total;
 }
 
 extern "C" int dgn_agg_forward(const DgnGraph* g, const DgnAggSpec* spec, const DgnMsg* msg, const float* w, int64_t ld_w,
@@ -277,10 +285,9 @@ extern "C" int dgn_agg_forward_aux(const DgnGraph* g, const DgnAggSpec* spec, co
     int rc = validate(g, spec, msg, w, log_deg);
     if (rc) return rc;
     if (g->n_nodes == 0) return DGN_OK;
-    const int64_t width = (int64_t)spec->n_scalers * (spec->agg_total > 0 ? spec->agg_total : spec->n_agg) *
-                          (spec->tower_stride > 0 ? msg->F / spec->n_towers : msg->F);
-    if (!out || ld_out < width) { set_error("out is null or ld_out too small"); return DGN_ERR_INVALID; }
-    if (g->n_hub > 0 && (!ws || ws_bytes < hub_ws_bytes(g, spec, msg->F))) { set_error("workspace too small: need %zu bytes", hub_ws_bytes(g, spec, msg->F)); return DGN_ERR_WORKSPACE; }
+    if (!out || ld_out < out_width(spec, msg->F)) { set_error("out is null or ld_out too small"); return DGN_ERR_INVALID; }
+    const AggWs s = agg_ws(g, spec, msg->F, false, 0);
+    if (g->n_hub > 0 && (!ws || ws_bytes < s.total)) { set_error("workspace too small: need %zu bytes", s.total); return DGN_ERR_WORKSPACE; }
     AggParams p;
     fill_params(p, g, spec, msg, w, ld_w, log_deg);
     if (ld_out > INT32_MAX) { set_error("ld_out must fit in int32"); return DGN_ERR_INVALID; }
@@ -290,7 +297,7 @@ extern "C" int dgn_agg_forward_aux(const DgnGraph* g, const DgnAggSpec* spec, co
         p.aux = aux;
         p.aux_rows = agg_aux_is_rows(p);
     }
-    if (g->n_hub > 0) carve_ws(p, g, spec, ws);
+    if (g->n_hub > 0) carve_hub(p, s, ws);
     const int vec = pick_vec(spec, msg, out, ld_out, nullptr);
     const unsigned tiles = (unsigned)((msg->F + kWave * vec - 1) / (kWave * vec));
     return launch(vec, p, tiles, static_cast<hipStream_t>(stream_), false);
@@ -306,10 +313,10 @@ int agg_backward_prepare(AggParams& p, const DgnGraph* g, const DgnAggSpec* spec
     int rc = validate(g, spec, msg, w, log_deg);
     if (rc) return rc;
     if (!grads) { set_error("null grads"); return DGN_ERR_INVALID; }
-    const int64_t width = (int64_t)spec->n_scalers * (spec->agg_total > 0 ? spec->agg_total : spec->n_agg) *
-                          (spec->tower_stride > 0 ? msg->F / spec->n_towers : msg->F);
-    if (!lds_gout && (!g_out || ld_gout < width)) { set_error("g_out is null or ld_gout too small"); return DGN_ERR_INVALID; }
-    if (g->n_hub > 0 && (!ws || ws_bytes < hub_ws_bytes(g, spec, msg->F))) { set_error("workspace too small: need %zu bytes", hub_ws_bytes(g, spec, msg->F)); return DGN_ERR_WORKSPACE; }
+    if (!lds_gout && (!g_out || ld_gout < out_width(spec, msg->F))) { set_error("g_out is null or ld_gout too small"); return DGN_ERR_INVALID; }
+    // (the whole layout; how far the caller's workspace reaches into it decides below)
+    const AggWs s = agg_ws(g, spec, msg->F, true, msg->edge_type ? msg->n_edge_types : 0);
+    if (g->n_hub > 0 && (!ws || ws_bytes < s.hub)) { set_error("workspace too small: need %zu bytes", s.hub); return DGN_ERR_WORKSPACE; }
     fill_params(p, g, spec, msg, w, ld_w, log_deg);
     if (ld_gout > INT32_MAX || grads->ld_src > INT32_MAX || grads->ld_dst > INT32_MAX || grads->ld_edge > INT32_MAX || grads->ld_in > INT32_MAX) { set_error("strides must fit in int32"); return DGN_ERR_INVALID; }
     p.g_out = g_out; p.ld_gout = (int32_t)ld_gout;
@@ -322,20 +329,18 @@ int agg_backward_prepare(AggParams& p, const DgnGraph* g, const DgnAggSpec* spec
         p.aux = const_cast<unsigned char*>(aux);
         p.aux_rows = agg_aux_is_rows(p);
     }
-    if (g->n_hub > 0) carve_ws(p, g, spec, ws);
+    if (g->n_hub > 0) carve_hub(p, s, ws);
     // atomic-free scatter when the transposed view and the [E, F] staging buffer are available
-    if (p.g_src && g->csc_ptr && g->csc_pos && g->n_edges > 0 && ws &&
-        ws_bytes >= hub_ws_bytes(g, spec, msg->F) + stage_bytes(g, msg->F)) {
-        p.stage = reinterpret_cast<float*>(static_cast<char*>(ws) + hub_ws_bytes(g, spec, msg->F));
+    if (p.g_src && g->csc_ptr && g->csc_pos && g->n_edges > 0 && ws && ws_bytes >= s.scatter) {
+        p.stage = s.stage.in<float>(ws);
         p.csc_ptr = g->csc_ptr; p.csc_pos = g->csc_pos;
     }
     float* tab_part = nullptr;
     if (msg->edge_type) {
         // the table's gradient is a reduction of the staged rows by type (after the sweep): the sweep itself writes no g_edge
-        const size_t need = hub_ws_bytes(g, spec, msg->F) + stage_bytes(g, msg->F) + edge_table_ws_bytes(msg->F, msg->n_edge_types);
-        if (!p.stage || ws_bytes < need) { set_error("edge-type table: the backward needs the two-phase scatter (g_src, g->csc_*) and a workspace of %zu bytes", need); return DGN_ERR_WORKSPACE; }
+        if (!p.stage || ws_bytes < s.total) { set_error("edge-type table: the backward needs the two-phase scatter (g_src, g->csc_*) and a workspace of %zu bytes", s.total); return DGN_ERR_WORKSPACE; }
         if (msg->F % 2 != 0) { set_error("edge-type table: F must be even"); return DGN_ERR_INVALID; }
-        tab_part = reinterpret_cast<float*>(static_cast<char*>(ws) + hub_ws_bytes(g, spec, msg->F) + stage_bytes(g, msg->F));
+        tab_part = s.tab_part.in<float>(ws);
         p.g_edge = nullptr;
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_);

@@ -21,7 +21,6 @@ constexpr size_t kLdsBytes = 160 * 1024;
 constexpr int kTailThreads = 512;
 
 inline int up4(int x) { return (x + 3) & ~3; }
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Dims {
     int type, has_pre, mixing, relu;
@@ -158,23 +157,23 @@ size_t tail_bwd_lds(const Dims& d) {
     return (size_t)(c4 + 4 * d.tail_rows * ldk + (d.mixing ? d.Fo * ldk : 0)) * 4;
 }
 
-struct FwdWs { size_t bn_part, total; };
+struct FwdWs { WsSpan bn_part; size_t total; };
 FwdWs fwd_ws(const Dims& d) {
+    WsLayout L;
     FwdWs w{};
-    w.bn_part = 0;
-    w.total = up256((size_t)d.n_blocks * 2 * d.Fo * sizeof(double));
+    w.bn_part = L.take((size_t)d.n_blocks * 2 * d.Fo * sizeof(double));
+    w.total = L.total;
     return w;
 }
-struct BwdWs { size_t g_y1, tail_part, tail_wpart, blk_part, total; };
+struct BwdWs { WsSpan tail_part, g_y1, tail_wpart, blk_part; size_t total; };
 BwdWs bwd_ws(const Dims& d) {
+    WsLayout L;
     BwdWs w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
-    w.tail_part = take((size_t)d.n_tail * 2 * d.Fo * sizeof(double));
-    w.g_y1 = take((size_t)d.N * d.Fo * 4);
-    w.tail_wpart = take((size_t)d.n_tail * d.n_tail_param * 4);
-    w.blk_part = take((size_t)d.n_blocks * d.n_blk_param * 4);
-    w.total = off;
+    w.tail_part = L.take((size_t)d.n_tail * 2 * d.Fo * sizeof(double));
+    w.g_y1 = L.take((size_t)d.N * d.Fo * 4);
+    w.tail_wpart = L.take((size_t)d.n_tail * d.n_tail_param * 4);
+    w.blk_part = L.take((size_t)d.n_blocks * d.n_blk_param * 4);
+    w.total = L.total;
     return w;
 }
 
@@ -341,7 +340,7 @@ extern "C" int dgn_block_layer_forward(const DgnBlockLayer* L, void* stream_) {
     if (!L->out || !L->running_mean || !L->running_var) { set_error("%s: null output / running statistics", fn); return DGN_ERR_INVALID; }
     const FwdWs w = fwd_ws(d);
     if (!L->ws || L->ws_bytes < w.total) { set_error("%s: workspace too small (%zu < %zu)", fn, L->ws_bytes, w.total); return DGN_ERR_WORKSPACE; }
-    p.bn_part = reinterpret_cast<double*>(static_cast<char*>(L->ws) + w.bn_part);
+    p.bn_part = w.bn_part.in<double>(L->ws);
     p.dbg_agg = L->dbg_agg; p.dbg_time = L->dbg_time;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     static LdsOptIn lds_ok{0};
@@ -362,12 +361,11 @@ extern "C" int dgn_block_layer_backward(const DgnBlockLayer* L, const DgnBlockGr
     DGN_TRY_RC(fill(p, L, d, true, fn));
     const BwdWs w = bwd_ws(d);
     if (!L->ws || L->ws_bytes < w.total) { set_error("%s: workspace too small (%zu < %zu)", fn, L->ws_bytes, w.total); return DGN_ERR_WORKSPACE; }
-    char* ws = static_cast<char*>(L->ws);
     p.g_out = G->g_out; p.g_h = G->g_h; p.g_gamma = G->g_gamma; p.g_beta = G->g_beta;
-    p.g_y1 = reinterpret_cast<float*>(ws + w.g_y1);
-    p.tail_part = reinterpret_cast<double*>(ws + w.tail_part);
-    p.tail_wpart = reinterpret_cast<float*>(ws + w.tail_wpart);
-    p.blk_part = reinterpret_cast<float*>(ws + w.blk_part);
+    p.g_y1 = w.g_y1.in<float>(L->ws);
+    p.tail_part = w.tail_part.in<double>(L->ws);
+    p.tail_wpart = w.tail_wpart.in<float>(L->ws);
+    p.blk_part = w.blk_part.in<float>(L->ws);
     p.dbg_gagg = L->dbg_gagg; p.dbg_time = L->dbg_time;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     static LdsOptIn lds_ok{0};

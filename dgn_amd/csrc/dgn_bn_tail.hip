@@ -522,7 +522,13 @@ void launch_bn_apply(hipStream_t stream, int64_t n_rows, int F, const float* x, 
     else hipLaunchKernelGGL(bn_apply_vec<1>, grid, dim3(256), 0, stream, n_rows, F, x, ld, gamma, beta, mean, invstd, running_mean, running_var, eps, relu, residual, y);
 }
 
-size_t part_bytes(int64_t n_rows, int F) { return (size_t)2 * F * stat_groups(n_rows, F) * sizeof(double); }
+// the workspace of the statistics passes: fp64 column partials of every workgroup, then the backward's two column sums (sums_out == NULL)
+struct TailWs { WsSpan part, sums; size_t total; };
+TailWs tail_ws(int64_t n_rows, int F) {
+    WsLayout L;
+    const WsSpan part = L.take((size_t)2 * F * stat_groups(n_rows, F) * sizeof(double), 8), sums = L.take((size_t)2 * F * sizeof(float), 4);
+    return {part, sums, L.total};
+}
 
 }  // namespace
 }  // namespace dgn
@@ -633,7 +639,7 @@ extern "C" int dgn_dropout_backward(int64_t n_elems, const float* g_y, const uns
 
 extern "C" size_t dgn_bn_tail_workspace_bytes(int64_t n_rows, int32_t F) {
     if (n_rows <= 0 || F < 1 || F > kMaxF) return 0;
-    return part_bytes(n_rows, F) + (size_t)2 * F * sizeof(float);
+    return tail_ws(n_rows, F).total;
 }
 
 extern "C" int dgn_bn_tail_forward(int64_t n_rows, int32_t F, const float* x, int64_t ld, const float* gamma, const float* beta,
@@ -678,8 +684,9 @@ int dgn::bn_tail_forward_nbt(int64_t n_rows, int32_t F, const float* x, int64_t 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (training) {
         if (!ws || !save_mean || !save_invstd) { set_error("dgn_bn_tail_forward: training needs ws, save_mean, save_invstd"); return DGN_ERR_INVALID; }
-        if (ws_bytes < dgn_bn_tail_workspace_bytes(n_rows, F)) { set_error("dgn_bn_tail_forward: workspace too small"); return DGN_ERR_WORKSPACE; }
-        double* part = static_cast<double*>(ws);
+        const TailWs s = tail_ws(n_rows, F);
+        if (ws_bytes < s.total) { set_error("dgn_bn_tail_forward: workspace too small"); return DGN_ERR_WORKSPACE; }
+        double* part = s.part.in<double>(ws);
         const int G = stat_groups(n_rows, F);
         if (pairs_ok(F, ld, x)) hipLaunchKernelGGL(bn_stats<true>, dim3(G), dim3(256), 0, stream, n_rows, F, x, ld, part, n_valid);
         else hipLaunchKernelGGL(bn_stats<false>, dim3(G), dim3(256), 0, stream, n_rows, F, x, ld, part, n_valid);
@@ -702,10 +709,11 @@ extern "C" int dgn_bn_tail_backward(int64_t n_rows, int32_t F, const float* g_y,
     if (n_rows < 0 || F < 1 || F > kMaxF || ld < F) { set_error("dgn_bn_tail_backward: bad shape (need 1 <= F <= 1024, ld >= F)"); return DGN_ERR_INVALID; }
     if (n_rows == 0) return DGN_OK;
     if (!g_y || !x || (!g_x && !sums_out) || !save_mean || !save_invstd || !ws) { set_error("dgn_bn_tail_backward: null buffer"); return DGN_ERR_INVALID; }
-    if (ws_bytes < dgn_bn_tail_workspace_bytes(n_rows, F)) { set_error("dgn_bn_tail_backward: workspace too small"); return DGN_ERR_WORKSPACE; }
+    const TailWs s = tail_ws(n_rows, F);
+    if (ws_bytes < s.total) { set_error("dgn_bn_tail_backward: workspace too small"); return DGN_ERR_WORKSPACE; }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    double* part = static_cast<double*>(ws);
-    float* sums = sums_out ? sums_out : reinterpret_cast<float*>(static_cast<char*>(ws) + part_bytes(n_rows, F));
+    double* part = s.part.in<double>(ws);
+    float* sums = sums_out ? sums_out : s.sums.in<float>(ws);
     const int G = stat_groups(n_rows, F);
     // (flat 16-byte chunks: odd widths of batches that fill the chip -- tools/bn_flat_vs_column.py: [275 k, 75] 47.0 -> 41.4 us, but [52 k, 70] 18.7 -> 23.0
     //  and [15 k, 65] 10.9 -> 14.1 against the thread-per-column(-pair) kernels, whose fold at the end of a workgroup is shorter)
@@ -748,8 +756,9 @@ extern "C" int dgn_bias_act_backward(int64_t n_rows, int32_t F, const float* g_y
         return DGN_OK;
     }
     if (!g_y || !x || !g_x || !ws) { set_error("dgn_bias_act_backward: null buffer"); return DGN_ERR_INVALID; }
-    if (ws_bytes < dgn_bn_tail_workspace_bytes(n_rows, F)) { set_error("dgn_bias_act_backward: workspace too small (dgn_bn_tail_workspace_bytes)"); return DGN_ERR_WORKSPACE; }
-    double* part = static_cast<double*>(ws);
+    const TailWs s = tail_ws(n_rows, F);
+    if (ws_bytes < s.total) { set_error("dgn_bias_act_backward: workspace too small (dgn_bn_tail_workspace_bytes)"); return DGN_ERR_WORKSPACE; }
+    double* part = s.part.in<double>(ws);
     const int G = stat_groups(n_rows, F);
     if (pairs_ok(F, ld, x, g_y, g_x)) hipLaunchKernelGGL(bias_act_bwd<true>, dim3(G), dim3(256), 0, stream, n_rows, F, g_y, x, ld, bias, act, slope, g_x, part);
     else hipLaunchKernelGGL(bias_act_bwd<false>, dim3(G), dim3(256), 0, stream, n_rows, F, g_y, x, ld, bias, act, slope, g_x, part);

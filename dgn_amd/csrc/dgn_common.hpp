@@ -44,6 +44,26 @@ inline hipError_t allow_lds(LdsOptIn& done, int bytes, K*... kernels) {
 int n_cus();
 inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
+// ---- global-memory workspaces: an entry point states its layout ONCE, as a function that returns a struct of named spans and `total`;
+// the exported *_workspace_bytes() query, the size check and the carve all read that struct ----------------------------------------------
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// a part of a workspace: `bytes` from `at`, all of them the part's own (the size asked for, rounded up to the alignment it was taken with)
+struct WsSpan {
+    size_t at, bytes;
+    template <class T> T* in(void* ws) const { return reinterpret_cast<T*>(static_cast<char*>(ws) + at); }
+};
+// the parts in order, each padded to `align` bytes (a power of two): the first starts at the workspace's base
+struct WsLayout {
+    size_t total = 0;
+    WsSpan take(size_t bytes, size_t align = 256) { const WsSpan s{total, (bytes + align - 1) & ~(align - 1)}; total += s.bytes; return s; }
+};
+// the check of an entry point (`who`: its name for the error text); align: 4 (float partials) or 8 (fp64 / int64 slots)
+inline bool workspace_ok(const char* who, const void* ws, size_t ws_bytes, size_t need, int align) {
+    if (ws && ws_bytes >= need && !(reinterpret_cast<uintptr_t>(ws) & (uintptr_t)(align - 1))) return true;
+    set_error("%s: workspace of %zu bytes%s required, got %zu", who, need, align == 8 ? " (8-byte aligned)" : "", ws_bytes);
+    return false;
+}
+
 // n items over at most max_groups workgroups of at least min_per items each: `per` items per workgroup, `groups` workgroups that have
 // some (0 for n = 0: the callers that launch one regardless clamp it), and `bound` >= groups, the count a workspace of one slot per
 // workgroup is sized by

@@ -36,6 +36,16 @@ WgPlan wgrad_plan(int64_t n_units, int k, int n) {
     return w;
 }
 
+// The weight gradient's workspace: the partial tiles, then a mask word per slot.  `total` keeps the size the query has always had -- the
+// two parts and 256 bytes for the rounding between them, no less than where run_mask ends -- because dgn_dense_layer_backward places
+// its last span behind this workspace
+struct WgWs { WsSpan part, run_mask; size_t total; };
+WgWs wgrad_ws(const WgPlan& w) {
+    WsLayout L;
+    const WsSpan part = L.take(w.part_floats * sizeof(float)), run_mask = L.take((size_t)w.slots * sizeof(uint32_t), 4);
+    return {part, run_mask, w.part_floats * sizeof(float) + run_mask.bytes + 256};
+}
+
 template <int NTN, int KT>
 hipError_t launch_wgrad_t(const DcWgradParams& p, dim3 grid, size_t lds, hipStream_t st) {
     static LdsOptIn lds_ok{0};
@@ -179,8 +189,7 @@ int dgn::dc::gemm_stats(const DgnDegreeClasses* d, int32_t k, int32_t n, int32_t
 
 extern "C" size_t dgn_dc_wgrad_workspace_bytes(int64_t n_units, int32_t k, int32_t n) {
     if (n_units <= 0 || !dgn_dc_wgrad_supported(k, n)) return 0;
-    const WgPlan w = wgrad_plan(n_units, k, n);
-    return w.part_floats * sizeof(float) + (size_t)w.slots * sizeof(uint32_t) + 256;
+    return wgrad_ws(wgrad_plan(n_units, k, n)).total;
 }
 
 extern "C" int dgn_dc_wgrad(const DgnDegreeClasses* d, int32_t S, int32_t k, int32_t n, const float* g, int64_t ldg, const float* x, int64_t ldx,
@@ -193,13 +202,13 @@ extern "C" int dgn_dc_wgrad(const DgnDegreeClasses* d, int32_t S, int32_t k, int
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (d->n_units == 0) return layout ? zero_rows_async(g_wf, n, layout->ld, layout->ld, st) : zero_rows_async(g_wf, (int64_t)S * n, k, ldw, st);
     if (!g || !x || ldg < n || ldx < k) { set_error("%s: null operand or row stride smaller than the row", fn); return DGN_ERR_INVALID; }
-    const size_t need = dgn_dc_wgrad_workspace_bytes(d->n_units, k, n);
-    if (!ws || ws_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, ws_bytes, need); return DGN_ERR_WORKSPACE; }
     const WgPlan w = wgrad_plan(d->n_units, k, n);
+    const WgWs s = wgrad_ws(w);
+    if (!ws || ws_bytes < s.total) { set_error("%s: workspace too small (%zu < %zu)", fn, ws_bytes, s.total); return DGN_ERR_WORKSPACE; }
     DcWgradParams p{};
     p.n_units = d->n_units; p.vperm = d->vperm; p.unit_class = d->unit_class; p.n = n; p.k = k; p.G = g; p.ldg = ldg; p.X = x; p.ldx = ldx;
-    p.part = static_cast<float*>(ws);
-    p.run_mask = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + ((w.part_floats * sizeof(float) + 255) & ~(size_t)255));
+    p.part = s.part.in<float>(ws);
+    p.run_mask = s.run_mask.in<uint32_t>(ws);
     p.k_slice = w.k_slice; p.kpad = w.kpad; p.slots = w.slots; p.units_per_block = w.units_per_block;
     const DgnDcLayout none{};
     const DgnDcLayout lay = layout ? *layout : none;

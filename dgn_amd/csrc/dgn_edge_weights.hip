@@ -461,10 +461,13 @@ __global__ __launch_bounds__(kBlock) void ew_hub_slice_write(const EwParams p) {
     range_write(st, p, row, beg, end);
 }
 
-size_t ws_bytes_for(const DgnGraph* g) {
-    if (!g || g->n_hub <= 0) return 0;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return up((size_t)g->n_chunks * DGN_MAX_CH * 5 * sizeof(float)) + up((size_t)g->n_hub * DGN_MAX_CH * 5 * sizeof(float));
+// the hub rows' workspace (graphs with hub rows only): the statistics of every chunk, then of every hub row
+struct HubWs { WsSpan slice_stats, hub_stats; size_t total; };
+HubWs hub_ws(const DgnGraph* g) {
+    WsLayout L;
+    if (!g || g->n_hub <= 0) return {};
+    const WsSpan slices = L.take((size_t)g->n_chunks * DGN_MAX_CH * 5 * sizeof(float)), hubs = L.take((size_t)g->n_hub * DGN_MAX_CH * 5 * sizeof(float));
+    return {slices, hubs, L.total};
 }
 
 }  // namespace
@@ -474,7 +477,7 @@ using namespace dgn;
 
 extern "C" size_t dgn_edge_weights_workspace_bytes(const DgnGraph* g, int32_t n_ch) {
     (void)n_ch;
-    return ws_bytes_for(g);
+    return hub_ws(g).total;
 }
 
 extern "C" int dgn_edge_weights(const DgnGraph* g, const float* eig, const float* eig_s_edge, const float* eig_d_edge,
@@ -490,7 +493,8 @@ extern "C" int dgn_edge_weights(const DgnGraph* g, const float* eig, const float
         if (ch[c].eig_col < 0 || ch[c].eig_col >= ld_eig) { set_error("channel %d: eig column %d outside 0..%lld", c, ch[c].eig_col, (long long)ld_eig - 1); return DGN_ERR_INVALID; }
     }
     if (g->n_nodes == 0 || g->n_edges == 0) return DGN_OK;
-    if (g->n_hub > 0 && (!ws || ws_bytes < ws_bytes_for(g))) { set_error("workspace too small: need %zu bytes", ws_bytes_for(g)); return DGN_ERR_WORKSPACE; }
+    const HubWs s = hub_ws(g);
+    if (g->n_hub > 0 && (!ws || ws_bytes < s.total)) { set_error("workspace too small: need %zu bytes", s.total); return DGN_ERR_WORKSPACE; }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     EwParams p{};
     p.indptr = g->indptr; p.src = g->src; p.n_nodes = g->n_nodes; p.row_base = g->row_base;
@@ -512,9 +516,8 @@ extern "C" int dgn_edge_weights(const DgnGraph* g, const float* eig, const float
     }
     p.w = w; p.ld_w = ld_w;
     if (g->n_hub > 0) {
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        p.slice_stats = static_cast<float*>(ws);
-        p.hub_stats = reinterpret_cast<float*>(static_cast<char*>(ws) + up((size_t)g->n_chunks * DGN_MAX_CH * 5 * sizeof(float)));
+        p.slice_stats = s.slice_stats.in<float>(ws);
+        p.hub_stats = s.hub_stats.in<float>(ws);
     }
     // (round 6: 2^20 -> 2^19 rows.  Below it the three classes are one launch of N / 64 + N / 4 + N one-wave workgroups, most of which
     //  leave at once: at 960 k k-NN rows (c3_mega) the dispatcher alone is 0.26 ms of a 0.383-ms launch; the ballot path takes 0.139)

@@ -15,7 +15,6 @@
 namespace dgn {
 namespace {
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline unsigned blocks(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 inline int bits_for(int64_t n) { int b = 1; while (((int64_t)1 << b) < n && b < 31) ++b; return b; }
 
@@ -99,15 +98,28 @@ size_t cub_bytes(int64_t n) {
     return up256(std::max(std::max(a, b), c)) + 256;
 }
 
+// The workspace of the three entry points (each uses the blocks it needs, by name): four int32 arrays per edge (sort keys / values, in
+// and out), four per node (+ 2: degrees, histograms, the cuts' running sums), a byte per edge of flags, and the primitives' own storage,
+// which is the last span and takes whatever the caller's buffer has beyond its start
+struct BuildWs { WsSpan edge[4], node[4], flags, cub; size_t total; };
+BuildWs build_ws(int64_t n_nodes, int64_t n_edges) {
+    WsLayout L;
+    BuildWs s{};
+    for (WsSpan& e : s.edge) e = L.take((size_t)(n_edges + 1) * 4);
+    for (WsSpan& v : s.node) v = L.take((size_t)(n_nodes + 2) * 4);
+    s.flags = L.take((size_t)n_edges + 1);
+    s.cub = L.take(cub_bytes((n_nodes + 2 > n_edges ? n_nodes + 2 : n_edges) + 1), 1);
+    s.total = L.total;
+    return s;
+}
+
 }  // namespace
 }  // namespace dgn
 
 using namespace dgn;
 
 extern "C" size_t dgn_graph_build_workspace_bytes(int64_t n_nodes, int64_t n_edges) {
-    const int64_t m = (n_nodes + 2 > n_edges ? n_nodes + 2 : n_edges) + 1;
-    // keys in / values in / values out / flags + scratch per node, + the primitives' own storage
-    return cub_bytes(m) + 4 * up256((size_t)(n_edges + 1) * 4) + 4 * up256((size_t)(n_nodes + 2) * 4) + up256((size_t)n_edges + 1);
+    return build_ws(n_nodes, n_edges).total;
 }
 
 extern "C" int dgn_graph_build(int64_t n_nodes, int64_t n_edges, const int64_t* src, const int64_t* dst, int32_t* indptr,
@@ -116,19 +128,12 @@ extern "C" int dgn_graph_build(int64_t n_nodes, int64_t n_edges, const int64_t* 
     const char* fn = "dgn_graph_build";
     if (n_nodes < 0 || n_edges < 0 || n_nodes >= INT32_MAX - 1 || n_edges >= INT32_MAX - 1) { set_error("%s: sizes outside the int32 CSR range", fn); return DGN_ERR_INVALID; }
     if (!indptr || !log_deg || !stats || (n_edges > 0 && (!src || !dst || !src_csr || !dst_csr || !eid))) { set_error("%s: null array", fn); return DGN_ERR_INVALID; }
-    if (!ws || ws_bytes < dgn_graph_build_workspace_bytes(n_nodes, n_edges)) { set_error("%s: workspace too small", fn); return DGN_ERR_WORKSPACE; }
+    const BuildWs s = build_ws(n_nodes, n_edges);
+    if (!ws || ws_bytes < s.total) { set_error("%s: workspace too small", fn); return DGN_ERR_WORKSPACE; }
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    char* w = static_cast<char*>(ws);
-    const size_t eb = up256((size_t)(n_edges + 1) * 4), nbytes = up256((size_t)(n_nodes + 2) * 4);
-    int32_t* key = reinterpret_cast<int32_t*>(w); w += eb;
-    int32_t* val = reinterpret_cast<int32_t*>(w); w += eb;
-    int32_t* perm = reinterpret_cast<int32_t*>(w); w += eb;
-    w += eb;
-    int32_t* deg = reinterpret_cast<int32_t*>(w); w += nbytes;
-    w += 3 * nbytes;
-    w += up256((size_t)n_edges + 1);
-    void* cub = w;
-    size_t cub_sz = ws_bytes - (size_t)(w - static_cast<char*>(ws));
+    int32_t *key = s.edge[0].in<int32_t>(ws), *val = s.edge[1].in<int32_t>(ws), *perm = s.edge[2].in<int32_t>(ws), *deg = s.node[0].in<int32_t>(ws);
+    void* cub = s.cub.in<void>(ws);
+    size_t cub_sz = ws_bytes - s.cub.at;
     DGN_HIP_CHECK(hipMemsetAsync(deg, 0, (size_t)(n_nodes + 1) * 4, st));
     DGN_HIP_CHECK(hipMemsetAsync(stats, 0, 4 * sizeof(int32_t), st));
     if (n_edges > 0) hipLaunchKernelGGL(gb_prepare, dim3(blocks(n_edges)), dim3(256), 0, st, n_edges, dst, key, val, deg);
@@ -148,15 +153,12 @@ extern "C" int dgn_graph_build_cuts(int64_t n_nodes, int64_t n_edges, const int3
     const char* fn = "dgn_graph_build_cuts";
     if (n_nodes < 0 || n_edges < 0 || n_nodes >= INT32_MAX - 1) { set_error("%s: sizes outside the int32 CSR range", fn); return DGN_ERR_INVALID; }
     if (!blk_cut || !gap_out || (n_edges > 0 && (!src_csr || !dst_csr))) { set_error("%s: null array", fn); return DGN_ERR_INVALID; }
-    if (!ws || ws_bytes < dgn_graph_build_workspace_bytes(n_nodes, n_edges)) { set_error("%s: workspace too small", fn); return DGN_ERR_WORKSPACE; }
+    const BuildWs s = build_ws(n_nodes, n_edges);
+    if (!ws || ws_bytes < s.total) { set_error("%s: workspace too small", fn); return DGN_ERR_WORKSPACE; }
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    char* w = static_cast<char*>(ws);
-    const size_t nbytes = up256((size_t)(n_nodes + 2) * 4);
-    int32_t* diff = reinterpret_cast<int32_t*>(w); w += nbytes;
-    int32_t* cross = reinterpret_cast<int32_t*>(w); w += nbytes;
-    int32_t* val = reinterpret_cast<int32_t*>(w); w += nbytes;
-    void* cub = w;
-    size_t cub_sz = ws_bytes - (size_t)(w - static_cast<char*>(ws));
+    int32_t *diff = s.node[0].in<int32_t>(ws), *cross = s.node[1].in<int32_t>(ws), *val = s.node[2].in<int32_t>(ws);
+    void* cub = s.cub.in<void>(ws);
+    size_t cub_sz = ws_bytes - s.cub.at;
     DGN_HIP_CHECK(hipMemsetAsync(diff, 0, (size_t)(n_nodes + 2) * 4, st));
     DGN_HIP_CHECK(hipMemsetAsync(gap_out, 0, sizeof(int32_t), st));
     if (n_edges > 0) hipLaunchKernelGGL(gb_span, dim3(blocks(n_edges)), dim3(256), 0, st, n_edges, src_csr, dst_csr, diff);
@@ -172,18 +174,12 @@ extern "C" int dgn_graph_build_csc(int64_t n_nodes, int64_t n_edges, const int32
                                    int32_t* csc_order, void* ws, size_t ws_bytes, void* stream_) {
     const char* fn = "dgn_graph_build_csc";
     if (!csc_ptr || (n_edges > 0 && (!src_csr || !csc_pos || !csc_order))) { set_error("%s: null array", fn); return DGN_ERR_INVALID; }
-    if (!ws || ws_bytes < dgn_graph_build_workspace_bytes(n_nodes, n_edges)) { set_error("%s: workspace too small", fn); return DGN_ERR_WORKSPACE; }
+    const BuildWs s = build_ws(n_nodes, n_edges);
+    if (!ws || ws_bytes < s.total) { set_error("%s: workspace too small", fn); return DGN_ERR_WORKSPACE; }
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    char* w = static_cast<char*>(ws);
-    const size_t eb = up256((size_t)(n_edges + 1) * 4), nbytes = up256((size_t)(n_nodes + 2) * 4);
-    int32_t* val = reinterpret_cast<int32_t*>(w); w += eb;
-    int32_t* key_out = reinterpret_cast<int32_t*>(w); w += eb;
-    w += 2 * eb;
-    int32_t* hist = reinterpret_cast<int32_t*>(w); w += nbytes;
-    w += 3 * nbytes;
-    w += up256((size_t)n_edges + 1);
-    void* cub = w;
-    size_t cub_sz = ws_bytes - (size_t)(w - static_cast<char*>(ws));
+    int32_t *val = s.edge[0].in<int32_t>(ws), *key_out = s.edge[1].in<int32_t>(ws), *hist = s.node[0].in<int32_t>(ws);
+    void* cub = s.cub.in<void>(ws);
+    size_t cub_sz = ws_bytes - s.cub.at;
     DGN_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)(n_nodes + 1) * 4, st));
     if (n_edges > 0) hipLaunchKernelGGL(gb_iota_hist, dim3(blocks(n_edges)), dim3(256), 0, st, n_edges, src_csr, val, hist);
     DGN_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(cub, cub_sz, hist, csc_ptr, (int)(n_nodes + 1), st));

@@ -20,7 +20,6 @@
 namespace dgn {
 namespace {
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 struct Dims {
@@ -236,21 +235,45 @@ DgnMsg sweep_msg(const DgnDenseLayer* L, const Dims& d, const float* hp) {
     return m;
 }
 
-struct BwdScratch { size_t g_z, sums, g_agg, g_wf, g_pq, g_hp, g_hq, g_wsd, g_bsd, bn_ws, comb_ws, wg_ws, agg_ws, total; };
-BwdScratch bwd_scratch(const DgnDenseLayer* L, const Dims& d) {
-    BwdScratch s{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
-    s.g_z = take((size_t)d.N * d.n * 4); s.sums = take((size_t)2 * d.fo * 4);
-    s.g_agg = take((size_t)d.N * d.K * 4); s.g_wf = take((size_t)d.n * d.K * 4);
-    s.g_pq = take(d.cx ? (size_t)d.N * 2 * d.Fp * 4 : 0); s.g_hp = take((size_t)d.N * d.Fp * 4); s.g_hq = take(d.cx ? (size_t)d.N * d.Fp * 4 : 0);
-    s.g_wsd = take(d.cx ? (size_t)2 * d.Fp * d.Fp * 4 : 0); s.g_bsd = take(d.cx ? (size_t)2 * d.Fp * 4 : 0);
-    s.bn_ws = take(dgn_bn_tail_workspace_bytes(d.N, d.fo));
-    s.comb_ws = take(dgn_scale_combine_backward_workspace_bytes(d.N, 1, d.fo));
-    s.wg_ws = take(std::max(d.dc ? dgn_dc_wgrad_workspace_bytes(L->dc->n_units, d.K, d.fo) : wgrad_ws(d.N, d.K, d.n),
-                            d.cx ? wgrad_ws(d.N, d.Fp, 2 * d.Fp) : (size_t)0));
-    s.agg_ws = take(dgn_agg_backward_workspace_bytes(L->graph, L->spec, d.Fp, 1));
-    s.total = off;
+// The layer's persistent folded-weight buffers, which the forward fills and the backward reads: where each region starts, in floats.
+// The allocating side is ops.py: _dense_sizes.
+//   L->wf   the folded posttrans weight [n][K] | its transpose [K][n] | degree-class route: the per-class weights [classes][fo][K] | their
+//           transposes [classes][K][fo]
+//   L->wsd  (complex) the folded pretrans weight [2 Fp][Fp] | its transpose [Fp][2 Fp] | the bias [2 Fp]
+struct Folded { size_t wft, wc, wct, wsdt, bsd; };
+Folded folded(const Dims& d) {
+    const size_t nK = (size_t)d.n * d.K, classes = (size_t)DGN_DC_CLASSES * d.fo * d.K, pre = (size_t)2 * d.Fp * d.Fp;
+    return {nK, 2 * nK, 2 * nK + classes, pre, 2 * pre};
+}
+
+// The forward workspace.  z: the posttrans product before the scalers combine it (not on the degree-class route); bn: BatchNorm's
+// statistics -- bn_stats' partials, or the slots the degree-class product's epilogue fills (dc::gemm_stats), or the combine pass' (one
+// slot per slab, at most 2 048 slabs ride); agg: the sweep's
+struct FwdWs { WsSpan z, bn, agg; size_t total; };
+FwdWs fwd_ws(const DgnDenseLayer* L, const Dims& d) {
+    WsLayout w;
+    const WsSpan z = w.take(d.dc ? 0 : (size_t)d.N * d.n * 4);
+    const WsSpan bn = w.take(std::max(dgn_bn_tail_workspace_bytes(d.N, d.fo), d.dc ? dc::gemm_stats_bytes(d.fo) : (size_t)2 * d.fo * 2048 * sizeof(double)));
+    const WsSpan agg = w.take(dgn_agg_workspace_bytes(L->graph, L->spec, d.Fp));
+    return {z, bn, agg, w.total};
+}
+
+// The backward workspace: the intermediate gradients, then the workspaces of the calls it makes (wg_ws: the posttrans weight gradient's and,
+// after it, the pretrans one's)
+struct BwdWs { WsSpan g_z, sums, g_agg, g_wf, g_pq, g_hp, g_hq, g_wsd, g_bsd, bn_ws, comb_ws, wg_ws, agg_ws; size_t total; };
+BwdWs bwd_ws(const DgnDenseLayer* L, const Dims& d) {
+    BwdWs s{};
+    WsLayout w;
+    s.g_z = w.take((size_t)d.N * d.n * 4); s.sums = w.take((size_t)2 * d.fo * 4);
+    s.g_agg = w.take((size_t)d.N * d.K * 4); s.g_wf = w.take((size_t)d.n * d.K * 4);
+    s.g_pq = w.take(d.cx ? (size_t)d.N * 2 * d.Fp * 4 : 0); s.g_hp = w.take((size_t)d.N * d.Fp * 4); s.g_hq = w.take(d.cx ? (size_t)d.N * d.Fp * 4 : 0);
+    s.g_wsd = w.take(d.cx ? (size_t)2 * d.Fp * d.Fp * 4 : 0); s.g_bsd = w.take(d.cx ? (size_t)2 * d.Fp * 4 : 0);
+    s.bn_ws = w.take(dgn_bn_tail_workspace_bytes(d.N, d.fo));
+    s.comb_ws = w.take(dgn_scale_combine_backward_workspace_bytes(d.N, 1, d.fo));
+    s.wg_ws = w.take(std::max(d.dc ? dgn_dc_wgrad_workspace_bytes(L->dc->n_units, d.K, d.fo) : wgrad_ws(d.N, d.K, d.n),
+                              d.cx ? wgrad_ws(d.N, d.Fp, 2 * d.Fp) : (size_t)0));
+    s.agg_ws = w.take(dgn_agg_backward_workspace_bytes(L->graph, L->spec, d.Fp, 1));
+    s.total = w.total;
     return s;
 }
 
@@ -281,16 +304,10 @@ extern "C" int dgn_dense_layer_supported(int32_t type, int32_t f_in, int32_t f_o
            K >= 4 && K <= 4096 && n >= 4 && n <= 4096 && Fp >= 4;
 }
 
-// BatchNorm's part of the forward workspace: bn_stats' partials, or the slots the degree-class product's epilogue fills (dc::gemm_stats)
-// (... or the combine pass': one slot per slab, at most 2 048 slabs ride)
-static size_t fwd_bn_ws(const Dims& d) {
-    return up256(std::max(dgn_bn_tail_workspace_bytes(d.N, d.fo), d.dc ? dc::gemm_stats_bytes(d.fo) : (size_t)2 * d.fo * 2048 * sizeof(double)));
-}
-
 extern "C" size_t dgn_dense_layer_forward_workspace_bytes(const DgnDenseLayer* L) {
     Dims d;
     if (!dims_of(L, d, "dgn_dense_layer_forward_workspace_bytes")) return 0;
-    return up256(d.dc ? 0 : (size_t)d.N * d.n * 4) + fwd_bn_ws(d) + up256(dgn_agg_workspace_bytes(L->graph, L->spec, d.Fp));
+    return fwd_ws(L, d).total;
 }
 
 extern "C" int dgn_dense_layer_forward(const DgnDenseLayer* L, void* stream) {
@@ -301,11 +318,12 @@ extern "C" int dgn_dense_layer_forward(const DgnDenseLayer* L, void* stream) {
     const bool padded = d.Fp != d.F0;
     if (!L->h || !L->w_post || !L->agg || !L->y || !L->wf || !L->out || !L->save_mean || !L->save_invstd || (padded && !L->hp) ||
         (d.S > 1 && !L->scale) || (d.cx && (!L->w_pre || !L->pq || !L->wsd))) { set_error("%s: null operand", fn); return DGN_ERR_INVALID; }
-    if (L->ws_bytes < dgn_dense_layer_forward_workspace_bytes(L) || !L->ws) { set_error("%s: workspace too small", fn); return DGN_ERR_WORKSPACE; }
+    const FwdWs s = fwd_ws(L, d);
+    if (L->ws_bytes < s.total || !L->ws) { set_error("%s: workspace too small", fn); return DGN_ERR_WORKSPACE; }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(L->ws);
-    float* z = reinterpret_cast<float*>(ws);
-    const size_t z_b = up256(d.dc ? 0 : (size_t)d.N * d.n * 4), bn_b = fwd_bn_ws(d);
+    float* z = s.z.in<float>(L->ws);
+    double* bn_part = s.bn.in<double>(L->ws);
+    const Folded fw = folded(d);
     const float* hp = L->h;
     if (padded && !odd_direct(L, d)) {
         if (d.Fp >= 4 && d.Fp - d.F0 < 4 && (reinterpret_cast<uintptr_t>(L->hp) & 15) == 0)
@@ -316,15 +334,13 @@ extern "C" int dgn_dense_layer_forward(const DgnDenseLayer* L, void* stream) {
     }
     const int hoff = d.cx ? d.F0 : 0;
     const int64_t ld_post = hoff + (int64_t)d.S * d.A * d.F0;
-    float* wft = L->wf + (size_t)d.n * d.K;
     DgnDcLayout lay{};                              // (degree-class route: the kernels read / write the reference layout themselves)
     lay.n_agg = d.A; lay.f_pad = d.Fp; lay.f_in = d.F0; lay.h_off = hoff; lay.id_slot = d.cx ? L->id_slot : -1; lay.ld = ld_post;
     if (!d.dc)
         hipLaunchKernelGGL(fold_post, dim3(nblk((int64_t)d.n * d.K)), dim3(256), 0, st, d.S, d.fo, d.A, d.Ab, d.F0, d.Fp, hoff, d.cx ? L->id_slot : -1, ld_post,
-                           L->w_post, L->wf, wft);
+                           L->w_post, L->wf, L->wf + fw.wft);
     if (d.cx) {
-        float* wsdt = L->wsd + (size_t)2 * d.Fp * d.Fp;
-        float* bsd = wsdt + (size_t)2 * d.Fp * d.Fp;
+        float *wsdt = L->wsd + fw.wsdt, *bsd = L->wsd + fw.bsd;
         hipLaunchKernelGGL(fold_pre, dim3(nblk((int64_t)2 * d.Fp * d.Fp)), dim3(256), 0, st, d.F0, d.Fp, (int64_t)2 * d.F0, L->w_pre, L->b_pre, L->wsd, wsdt, bsd);
         DGN_HIP_CHECK(hipGetLastError());
         // P | Q = hp [W_s | W_d]^T + [0 | b]                                                    (dgn_layer.py:75-80, decomposed)
@@ -333,21 +349,20 @@ extern "C" int dgn_dense_layer_forward(const DgnDenseLayer* L, void* stream) {
     DGN_HIP_CHECK(hipGetLastError());
     // the sweep (+ the h_in pass-through block of the complex layer)                            (:86-98 / :161-173)
     const DgnMsg msg = sweep_msg(L, d, hp);
-    DGN_TRY(dgn_agg_forward_aux(L->graph, L->spec, &msg, L->w, L->ld_w, L->log_deg, L->agg, d.K, L->agg_aux, ws + z_b + bn_b, L->ws_bytes - z_b - bn_b,
+    DGN_TRY(dgn_agg_forward_aux(L->graph, L->spec, &msg, L->w, L->ld_w, L->log_deg, L->agg, d.K, L->agg_aux, s.agg.in<char>(L->ws), s.agg.bytes,
                                 stream));
     // posttrans with the folded scalers, bias and graph norm                                    (:116-122 / :187-193)
     if (d.dc) {
         // one product per in-degree class: y = snorm (b + agg W_class^T), W_class = sum_s scale_s(class) W_f[s]
-        float* wc = L->wf + (size_t)2 * d.n * d.K;
-        float* wct = wc + (size_t)DGN_DC_CLASSES * d.fo * d.K;
+        float *wc = L->wf + fw.wc, *wct = L->wf + fw.wct;
         DGN_TRY(dgn_dc_fold(L->dc, d.S, d.fo, d.K, 1, L->w_post, &lay, wc, wct, stream));
         // (round 6: BatchNorm's column sums of y ride in the product's epilogue -- no bn_stats pass; option bn_stats_fused)
         if (option(OPT_BN_STATS_FUSED) && !L->n_valid) {
             int slots = 0;
             DGN_TRY(dc::gemm_stats(L->dc, d.K, d.fo, 1, L->agg, d.K, 0, wc, d.K, (int64_t)d.fo * d.K, 0, L->b_post, L->snorm, L->y, d.fo, 0, 0,
-                                   reinterpret_cast<double*>(ws + z_b), bn_b, &slots, stream));
+                                   bn_part, s.bn.bytes, &slots, stream));
             // BatchNorm -> ReLU -> residual                                                     (:123-128 / :194-199)
-            if (slots > 0) return bn_tail_forward_from_partials(d.N, d.fo, slots, reinterpret_cast<const double*>(ws + z_b), L->y, d.fo, L->bn_gamma, L->bn_beta,
+            if (slots > 0) return bn_tail_forward_from_partials(d.N, d.fo, slots, bn_part, L->y, d.fo, L->bn_gamma, L->bn_beta,
                                                  L->running_mean, L->running_var, L->momentum, L->eps, 1, L->residual ? L->h : nullptr, L->out,
                                                  L->save_mean, L->save_invstd, L->num_batches_tracked, L->num_batches_tracked ? 1 : 0, stream);
         } else {
@@ -358,15 +373,15 @@ extern "C" int dgn_dense_layer_forward(const DgnDenseLayer* L, void* stream) {
         // (round 6: BatchNorm's column sums of y ride in the combine pass where its slabs fit the statistics workspace -- no bn_stats launch)
         int slots = 0;
         const bool ride = option(OPT_BN_STATS_FUSED) && !L->n_valid;
-        DGN_TRY(scale_combine_forward_stats(d.N, 1, d.S, d.fo, z, L->scale, L->b_post, L->snorm, L->y, d.fo, ride ? reinterpret_cast<double*>(ws + z_b) : nullptr,
-                                            bn_b, &slots, stream));
-        if (slots > 0) return bn_tail_forward_from_partials(d.N, d.fo, slots, reinterpret_cast<const double*>(ws + z_b), L->y, d.fo, L->bn_gamma, L->bn_beta,
+        DGN_TRY(scale_combine_forward_stats(d.N, 1, d.S, d.fo, z, L->scale, L->b_post, L->snorm, L->y, d.fo, ride ? bn_part : nullptr,
+                                            s.bn.bytes, &slots, stream));
+        if (slots > 0) return bn_tail_forward_from_partials(d.N, d.fo, slots, bn_part, L->y, d.fo, L->bn_gamma, L->bn_beta,
                                                             L->running_mean, L->running_var, L->momentum, L->eps, 1, L->residual ? L->h : nullptr, L->out,
                                                             L->save_mean, L->save_invstd, L->num_batches_tracked, L->num_batches_tracked ? 1 : 0, stream);
     }
     // BatchNorm -> ReLU -> residual                                                             (:123-128 / :194-199)
     DGN_TRY(bn_tail_forward_nbt(d.N, d.fo, L->y, d.fo, L->bn_gamma, L->bn_beta, L->running_mean, L->running_var, L->momentum, L->eps, 1, 1,
-                                L->residual ? L->h : nullptr, L->out, L->save_mean, L->save_invstd, ws + z_b, bn_b, L->n_valid, L->num_batches_tracked,
+                                L->residual ? L->h : nullptr, L->out, L->save_mean, L->save_invstd, bn_part, s.bn.bytes, L->n_valid, L->num_batches_tracked,
                                 L->num_batches_tracked ? 1 : 0, stream));
     return DGN_OK;
 }
@@ -374,7 +389,7 @@ extern "C" int dgn_dense_layer_forward(const DgnDenseLayer* L, void* stream) {
 extern "C" size_t dgn_dense_layer_backward_workspace_bytes(const DgnDenseLayer* L) {
     Dims d;
     if (!dims_of(L, d, "dgn_dense_layer_backward_workspace_bytes")) return 0;
-    return bwd_scratch(L, d).total;
+    return bwd_ws(L, d).total;
 }
 
 extern "C" int dgn_dense_layer_backward(const DgnDenseLayer* L, const DgnDenseGrads* G, void* stream) {
@@ -387,44 +402,41 @@ extern "C" int dgn_dense_layer_backward(const DgnDenseLayer* L, const DgnDenseGr
         set_error("%s: null gradient buffer", fn);
         return DGN_ERR_INVALID;
     }
-    const BwdScratch s = bwd_scratch(L, d);
+    const BwdWs s = bwd_ws(L, d);
     if (!L->ws || L->ws_bytes < s.total) { set_error("%s: workspace too small (%zu < %zu)", fn, L->ws_bytes, s.total); return DGN_ERR_WORKSPACE; }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(L->ws);
-    auto f = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    void* ws = L->ws;
+    auto f = [&](const WsSpan& part) { return part.in<float>(ws); };
     float *g_z = f(s.g_z), *sums = f(s.sums), *g_agg = f(s.g_agg), *g_wf = f(s.g_wf), *g_pq = f(s.g_pq), *g_hp = f(s.g_hp), *g_hq = f(s.g_hq),
           *g_wsd = f(s.g_wsd), *g_bsd = f(s.g_bsd);
     const bool padded = d.Fp != d.F0;
     const float* hp = padded ? L->hp : L->h;
     const int hoff = d.cx ? d.F0 : 0;
     const int64_t ld_post = hoff + (int64_t)d.S * d.A * d.F0;
-    const float* wft = L->wf + (size_t)d.n * d.K;
+    const Folded fw = folded(d);
     // BatchNorm (+ ReLU): column sums + affine gradients; its input gradient is formed inside the combine backward
     DGN_TRY(dgn_bn_tail_backward(d.N, d.fo, G->g_out, L->y, d.fo, L->bn_gamma, L->bn_beta, L->save_mean, L->save_invstd, 1, nullptr, G->g_gamma, G->g_beta,
-                                 sums, ws + s.bn_ws, dgn_bn_tail_workspace_bytes(d.N, d.fo), L->n_valid, stream));
+                                 sums, s.bn_ws.in<char>(ws), s.bn_ws.bytes, L->n_valid, stream));
     DgnBnGrad bn{};
     bn.g_out = G->g_out; bn.y = L->y; bn.ld = d.fo; bn.gamma = L->bn_gamma; bn.beta = L->bn_beta; bn.mean = L->save_mean; bn.invstd = L->save_invstd;
     bn.sums = sums; bn.relu = 1; bn.n_valid = L->n_valid;
     if (d.dc) {
         // g_t = snorm * (BatchNorm input gradient) [N, f_out]; per class: d agg = g_t W_class, G_class = g_t^T agg; g_wf = sum_class scale G_class
-        const float* wct = L->wf + (size_t)2 * d.n * d.K + (size_t)DGN_DC_CLASSES * d.fo * d.K;
-        DGN_TRY(scale_combine_backward_impl(d.N, 1, 1, d.fo, nullptr, 0, nullptr, L->snorm, g_z, G->g_b_post, ws + s.comb_ws,
-                                           dgn_scale_combine_backward_workspace_bytes(d.N, 1, d.fo), &bn, stream, 1));
+        DGN_TRY(scale_combine_backward_impl(d.N, 1, 1, d.fo, nullptr, 0, nullptr, L->snorm, g_z, G->g_b_post, s.comb_ws.in<char>(ws), s.comb_ws.bytes, &bn, stream, 1));
         static const int dc_stream = getenv("DGN_DC_STREAM") ? atoi(getenv("DGN_DC_STREAM")) : 0;      // (experiment: nontemporal d agg rows)
-        DGN_TRY(dgn_dc_gemm(L->dc, d.fo, d.K, 1, g_z, d.fo, 0, wct, d.fo, (int64_t)d.fo * d.K, 0, nullptr, nullptr, g_agg, d.K, 0, dc_stream, stream));
+        DGN_TRY(dgn_dc_gemm(L->dc, d.fo, d.K, 1, g_z, d.fo, 0, L->wf + fw.wct, d.fo, (int64_t)d.fo * d.K, 0, nullptr, nullptr, g_agg, d.K, 0, dc_stream, stream));
         DgnDcLayout lay{};
         lay.n_agg = d.A; lay.f_pad = d.Fp; lay.f_in = d.F0; lay.h_off = hoff; lay.id_slot = d.cx ? L->id_slot : -1; lay.ld = ld_post;
-        DGN_TRY(dgn_dc_wgrad(L->dc, d.S, d.K, d.fo, g_z, d.fo, L->agg, d.K, G->g_w_post, 0, &lay, ws + s.wg_ws,
-                             dgn_dc_wgrad_workspace_bytes(L->dc->n_units, d.K, d.fo), stream));
+        DGN_TRY(dgn_dc_wgrad(L->dc, d.S, d.K, d.fo, g_z, d.fo, L->agg, d.K, G->g_w_post, 0, &lay, s.wg_ws.in<char>(ws), s.wg_ws.bytes, stream));
     } else {
         // (one scaler: the bias gradient sum_m g_z[m, :] rides in the weight-gradient pass as its ones column -- no partial sums in the
         //  combine backward, no bias_finalize launch: round 6, the 19-launch CIFAR10 step)
         const bool bias_from_wgrad = d.S == 1 && !L->scale;      // (with a scale table sum_m g_z[m, :] carries the table's factors: not d bias)
-        DGN_TRY(scale_combine_backward_impl(d.N, 1, d.S, d.fo, nullptr, 0, L->scale, L->snorm, g_z, bias_from_wgrad ? nullptr : G->g_b_post, ws + s.comb_ws,
-                                           dgn_scale_combine_backward_workspace_bytes(d.N, 1, d.fo), &bn, stream, 1));
+        DGN_TRY(scale_combine_backward_impl(d.N, 1, d.S, d.fo, nullptr, 0, L->scale, L->snorm, g_z, bias_from_wgrad ? nullptr : G->g_b_post, s.comb_ws.in<char>(ws),
+                                           s.comb_ws.bytes, &bn, stream, 1));
         // posttrans: input gradient (on the transposed folded weight), weight gradient, un-folded into the reference's layout
-        DGN_TRY(lin_fwd(d.N, d.n, d.K, g_z, wft, nullptr, g_agg, stream));
-        DGN_TRY(lin_wgrad(d.N, d.K, d.n, g_z, L->agg, g_wf, bias_from_wgrad ? G->g_b_post : nullptr, ws + s.wg_ws, wgrad_ws(d.N, d.K, d.n), stream));
+        DGN_TRY(lin_fwd(d.N, d.n, d.K, g_z, L->wf + fw.wft, nullptr, g_agg, stream));
+        DGN_TRY(lin_wgrad(d.N, d.K, d.n, g_z, L->agg, g_wf, bias_from_wgrad ? G->g_b_post : nullptr, s.wg_ws.in<char>(ws), s.wg_ws.bytes, stream));
     }
     if (!d.dc)
         hipLaunchKernelGGL(unfold_post, dim3(nblk((int64_t)d.fo * ld_post)), dim3(256), 0, st, d.S, d.fo, d.A, d.Ab, d.F0, d.Fp, hoff, d.cx ? L->id_slot : 0, ld_post,
@@ -442,20 +454,19 @@ extern "C" int dgn_dense_layer_backward(const DgnDenseLayer* L, const DgnDenseGr
         gr.g_in = g_hp; gr.ld_in = d.Fp;
     }
     gr.accumulate = 0;
-    DGN_TRY(dgn_agg_backward_aux(L->graph, L->spec, &msg, L->w, L->ld_w, L->log_deg, g_agg, d.K, L->agg_aux, &gr, ws + s.agg_ws,
-                                 dgn_agg_backward_workspace_bytes(L->graph, L->spec, d.Fp, 1), stream));
+    DGN_TRY(dgn_agg_backward_aux(L->graph, L->spec, &msg, L->w, L->ld_w, L->log_deg, g_agg, d.K, L->agg_aux, &gr, s.agg_ws.in<char>(ws), s.agg_ws.bytes, stream));
     const float* g_res = L->residual ? G->g_out : nullptr;
     bool fused_dh = false;
     if (d.cx) {
         // pretrans P|Q Linear: input gradient (transposed weight), weight + bias gradient, un-folded
-        const float* wsdt = L->wsd + (size_t)2 * d.Fp * d.Fp;
+        const float* wsdt = L->wsd + fw.wsdt;
         // even hidden size: d h = (d h_in + (d P|Q) W_sd) + residual leaves as the product's epilogue (unpad_add's order of additions)
         const bool al16 = ((reinterpret_cast<uintptr_t>(g_pq) | reinterpret_cast<uintptr_t>(g_hp) | reinterpret_cast<uintptr_t>(G->g_h) |
                             reinterpret_cast<uintptr_t>(g_res)) & 15) == 0;
         fused_dh = d.Fp == d.F0 && al16 && dgn_linear_supported(2 * d.Fp, d.Fp, 0) && dgn_linear_add_supported(2 * d.Fp, d.Fp);
         if (fused_dh) DGN_TRY(dgn_linear_forward_add(d.N, 2 * d.Fp, d.Fp, g_pq, wsdt, 2 * d.Fp, 0, g_hp, g_res, G->g_h, stream));
         else DGN_TRY(lin_fwd(d.N, 2 * d.Fp, d.Fp, g_pq, wsdt, nullptr, g_hq, stream));
-        DGN_TRY(lin_wgrad(d.N, d.Fp, 2 * d.Fp, g_pq, hp, g_wsd, g_bsd, ws + s.wg_ws, wgrad_ws(d.N, d.Fp, 2 * d.Fp), stream));
+        DGN_TRY(lin_wgrad(d.N, d.Fp, 2 * d.Fp, g_pq, hp, g_wsd, g_bsd, s.wg_ws.in<char>(ws), s.wg_ws.bytes, stream));
         hipLaunchKernelGGL(unfold_pre, dim3(nblk((int64_t)2 * d.F0 * d.F0)), dim3(256), 0, st, d.F0, d.Fp, (int64_t)2 * d.F0, g_wsd, g_bsd, G->g_w_pre, G->g_b_pre);
     }
     // d h = d h_in (+ d x_src, same buffer) [+ (d P|Q) W_sd] [+ residual], un-padded

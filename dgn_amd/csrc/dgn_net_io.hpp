@@ -199,12 +199,7 @@ inline bool rows_in_range(const char* who, int64_t n_rows) {
     return false;
 }
 
-// align: 4 (float partials) or 8 (fp64 / int64 slots)
-inline bool workspace_ok(const char* who, const void* ws, size_t ws_bytes, size_t need, int align) {
-    if (ws && ws_bytes >= need && !(reinterpret_cast<uintptr_t>(ws) & (uintptr_t)(align - 1))) return true;
-    set_error("%s: workspace of %zu bytes%s required, got %zu", who, need, align == 8 ? " (8-byte aligned)" : "", ws_bytes);
-    return false;
-}
+using dgn::workspace_ok;      // (dgn_common.hpp, beside the workspace layout helpers)
 
 // the autograd backward of a loss that saved its gradient: g_scores = g_saved * *g_loss over n_rows x width (`what`: the width's name)
 inline int loss_backward(const char* who, const char* what, int64_t n_rows, int32_t width, const float* g_saved, int64_t ld_g,

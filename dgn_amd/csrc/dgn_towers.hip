@@ -16,8 +16,6 @@
 namespace dgn {
 namespace {
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // g_h = [g_res] + g_a + g_b   (the three contributions to d h: residual, h_in of the sweep, the P|Q input gradient)
 __global__ __launch_bounds__(256) void add3_rows(int64_t n4, const float4* __restrict__ res, const float4* __restrict__ a,
                                                  const float4* __restrict__ b, float4* __restrict__ out) {
@@ -165,13 +163,22 @@ extern "C" int dgn_towers_layer_zmask_supported(int32_t n_towers, int32_t f_out)
     return !off && n_towers >= 1 && f_out >= 1 && Fo % 16 != 0 && dgn_linear_add_supported(Fo, Fo) && dgn_linear_act_supported(Fo, Fo);
 }
 
-// BatchNorm's part of the forward workspace: bn_stats' partials, or the slots the posttrans product's epilogue fills (lin::combine_forward_stats)
-static size_t fwd_bn_ws(const Dims& d) { return up256(std::max(dgn_bn_tail_workspace_bytes(d.N, d.Fo), lin::combine_forward_stats_bytes(d.T, d.fo))); }
+namespace {
+// The forward workspace.  bn: BatchNorm's statistics -- bn_stats' partials, or the slots the posttrans product's epilogue fills
+// (lin::combine_forward_stats); agg: the sweep's
+struct FwdWs { WsSpan bn, agg; size_t total; };
+FwdWs fwd_ws(const DgnTowersLayer* L, const Dims& d) {
+    WsLayout w;
+    const WsSpan bn = w.take(std::max(dgn_bn_tail_workspace_bytes(d.N, d.Fo), lin::combine_forward_stats_bytes(d.T, d.fo)));
+    const WsSpan agg = w.take(dgn_agg_workspace_bytes(L->graph, L->spec, d.Fm));
+    return {bn, agg, w.total};
+}
+}  // namespace
 
 extern "C" size_t dgn_towers_layer_forward_workspace_bytes(const DgnTowersLayer* L) {
     Dims d;
     if (!dims_of(L, d, "dgn_towers_layer_forward_workspace_bytes")) return 0;
-    return fwd_bn_ws(d) + up256(dgn_agg_workspace_bytes(L->graph, L->spec, d.Fm));
+    return fwd_ws(L, d).total;
 }
 
 extern "C" int dgn_towers_layer_forward(const DgnTowersLayer* L, void* stream) {
@@ -182,29 +189,28 @@ extern "C" int dgn_towers_layer_forward(const DgnTowersLayer* L, void* stream) {
     if (!L->h || !L->w_sd || !L->w_post || !L->w_mix || !L->pq || !L->aggx || !L->y0 || (!L->z && !L->zmask) || !L->out || !L->save_mean ||
         !L->save_invstd || (d.S > 1 && !L->scale)) { set_error("%s: null operand", fn); return DGN_ERR_INVALID; }
     if (!drop_ok(L, fn, true)) return DGN_ERR_INVALID;
-    const size_t bn_ws = fwd_bn_ws(d);
-    if (L->ws_bytes < dgn_towers_layer_forward_workspace_bytes(L) || (!L->ws && L->ws_bytes)) { set_error("%s: workspace too small", fn); return DGN_ERR_WORKSPACE; }
-    char* ws = static_cast<char*>(L->ws);
+    const FwdWs s = fwd_ws(L, d);
+    if (L->ws_bytes < s.total || (!L->ws && L->ws_bytes)) { set_error("%s: workspace too small", fn); return DGN_ERR_WORKSPACE; }
+    double* bn_part = s.bn.in<double>(L->ws);
     // P | Q = h [W_s | W_d]^T + [0 | b]                                                     (dgn_layer.py:226-231, decomposed)
     // (block-diagonal weights: the towers' own [f_in, f_in] blocks only, where that kernel family has the shape)
     if (use_bd(L, d)) DGN_TRY(dgn_linear_bd_forward(d.N, d.T, d.fi, L->h, L->w_sd, d.Fm, L->bias_sd, L->pq, stream));
     else DGN_TRY(dgn_linear_forward(d.N, d.Fm, 2 * d.Fm, 1, L->h, d.Fm, 0, L->w_sd, d.Fm, 0, 0, L->bias_sd, 0, L->pq, 2 * d.Fm, 0, stream));
     // all towers' aggregators (+ the h_in block) in one sweep, tower-major                   (:237-249, :261-264)
     const DgnMsg msg = sweep_msg(L, d);
-    const size_t agg_ws = L->ws_bytes - bn_ws;
-    DGN_TRY(dgn_agg_forward_aux(L->graph, L->spec, &msg, L->w, L->ld_w, L->log_deg, L->aggx, d.K, L->agg_aux, ws + bn_ws, agg_ws, stream));
+    DGN_TRY(dgn_agg_forward_aux(L->graph, L->spec, &msg, L->w, L->ld_w, L->log_deg, L->aggx, d.K, L->agg_aux, s.agg.in<char>(L->ws), s.agg.bytes, stream));
     // posttrans([h || agg]) with the folded scalers, bias and graph norm                     (:266-271)
     // (round 6: BatchNorm's column sums of y0 ride in the product's epilogue where nothing else needs a pass over y0 -- no bn_stats launch)
     int stat_slots = 0;
     if (option(OPT_BN_STATS_FUSED) && !L->y1 && !L->n_valid) {
         const int rc = lin::combine_forward_stats(d.N, d.K, d.T, d.S, d.fo, L->aggx, d.N * d.K, L->w_post, d.K, (int64_t)d.S * d.fo * d.K, L->scale, L->b_post,
-                                                  L->snorm, L->y0, d.Fo, reinterpret_cast<double*>(ws), bn_ws, &stat_slots, stream);
+                                                  L->snorm, L->y0, d.Fo, bn_part, s.bn.bytes, &stat_slots, stream);
         if (rc < 0) return DGN_ERR_HIP;
         if (rc > 0) stat_slots = 0;
     }
     if (stat_slots > 0) {
         // the towers' BatchNorm (training statistics)                                        (:272-273)
-        DGN_TRY(bn_finalize_launch(d.N, d.Fo, stat_slots, reinterpret_cast<const double*>(ws), L->running_mean, L->running_var, L->momentum, L->eps,
+        DGN_TRY(bn_finalize_launch(d.N, d.Fo, stat_slots, bn_part, L->running_mean, L->running_var, L->momentum, L->eps,
                                    L->save_mean, L->save_invstd, L->num_batches_tracked, L->n_nbt, stream));
     } else {
     DGN_TRY(dgn_linear_combine_forward(d.N, d.K, d.T, d.S, d.fo, L->aggx, d.N * d.K, L->w_post, d.K, (int64_t)d.S * d.fo * d.K, L->scale,
@@ -212,7 +218,7 @@ extern "C" int dgn_towers_layer_forward(const DgnTowersLayer* L, void* stream) {
     // the towers' BatchNorm (training statistics)                                            (:272-273)
     // (y1 == NULL: statistics only -- the mixing Linear normalises y0 while it stages its strips, the normalised tensor is never written)
     DGN_TRY(bn_tail_forward_nbt(d.N, d.Fo, L->y0, d.Fo, L->bn_gamma, L->bn_beta, L->running_mean, L->running_var, L->momentum, L->eps, 1, 0,
-                                nullptr, L->y1, L->save_mean, L->save_invstd, ws, bn_ws, L->n_valid, L->num_batches_tracked, L->n_nbt, stream));
+                                nullptr, L->y1, L->save_mean, L->save_invstd, bn_part, s.bn.bytes, L->n_valid, L->num_batches_tracked, L->n_nbt, stream));
     }
     // the towers' dropout, on the normalised rows in place                                   (:275)
     if (L->drop_p > 0.0f) DGN_TRY(dgn_dropout_forward(d.N * d.Fo, L->y1, L->drop_p, L->drop_seed, L->drop_offset, L->y1, L->drop_mask, stream));
@@ -238,27 +244,26 @@ extern "C" int dgn_towers_layer_forward(const DgnTowersLayer* L, void* stream) {
 }
 
 namespace {
-struct BwdScratch {
-    size_t g_z, g_y1, sums, g_yr, g_aggx, g_pq, g_in, g_hpq, bn_ws, comb_ws, wg_mix, wg_post, wg_sd, agg_ws, dwx, g_sum, total;
-};
-BwdScratch bwd_scratch(const DgnTowersLayer* L, const Dims& d) {
-    BwdScratch s{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
+// The backward workspace: the intermediate gradients, then the workspaces of the calls it makes (wg_sd: whichever of the two P|Q
+// weight-gradient kernels runs)
+struct BwdWs { WsSpan g_z, g_y1, sums, g_yr, g_aggx, g_pq, g_in, g_hpq, bn_ws, comb_ws, wg_mix, wg_post, wg_sd, agg_ws, dwx, g_sum; size_t total; };
+BwdWs bwd_ws(const DgnTowersLayer* L, const Dims& d) {
+    BwdWs s{};
+    WsLayout w;
     const size_t NF = (size_t)d.N * d.Fo * 4;
-    s.g_z = take(NF); s.g_y1 = take(NF); s.sums = take((size_t)2 * d.Fo * 4);
-    s.g_yr = take(NF);
-    s.g_aggx = take((size_t)d.T * d.N * d.K * 4);
-    s.g_pq = take((size_t)d.N * 2 * d.Fm * 4); s.g_in = take((size_t)d.N * d.Fm * 4); s.g_hpq = take((size_t)d.N * d.Fm * 4);
-    s.bn_ws = take(dgn_bn_tail_workspace_bytes(d.N, d.Fo));
-    s.comb_ws = take(dgn_scale_combine_backward_workspace_bytes(d.N, d.T, d.fo));
-    s.wg_mix = take(dgn_linear_wgrad_workspace_bytes(d.N, d.Fo, d.Fo, 1));
-    s.wg_post = take(dgn_linear_wgrad_workspace_bytes(d.N, d.K, d.S * d.fo, d.T));
-    s.wg_sd = take(std::max(dgn_linear_wgrad_workspace_bytes(d.N, d.Fm, 2 * d.Fm, 1), dgn_linear_bd_wgrad_workspace_bytes(d.N, d.T, d.fi)));
-    s.agg_ws = take(dgn_agg_backward_workspace_bytes(L->graph, L->spec, d.Fm, 1));
-    s.dwx = take((size_t)d.Fo * d.Fo * 4);
-    s.g_sum = take((size_t)d.T * d.S * d.fo * 4);
-    s.total = off;
+    s.g_z = w.take(NF); s.g_y1 = w.take(NF); s.sums = w.take((size_t)2 * d.Fo * 4);
+    s.g_yr = w.take(NF);
+    s.g_aggx = w.take((size_t)d.T * d.N * d.K * 4);
+    s.g_pq = w.take((size_t)d.N * 2 * d.Fm * 4); s.g_in = w.take((size_t)d.N * d.Fm * 4); s.g_hpq = w.take((size_t)d.N * d.Fm * 4);
+    s.bn_ws = w.take(dgn_bn_tail_workspace_bytes(d.N, d.Fo));
+    s.comb_ws = w.take(dgn_scale_combine_backward_workspace_bytes(d.N, d.T, d.fo));
+    s.wg_mix = w.take(dgn_linear_wgrad_workspace_bytes(d.N, d.Fo, d.Fo, 1));
+    s.wg_post = w.take(dgn_linear_wgrad_workspace_bytes(d.N, d.K, d.S * d.fo, d.T));
+    s.wg_sd = w.take(std::max(dgn_linear_wgrad_workspace_bytes(d.N, d.Fm, 2 * d.Fm, 1), dgn_linear_bd_wgrad_workspace_bytes(d.N, d.T, d.fi)));
+    s.agg_ws = w.take(dgn_agg_backward_workspace_bytes(L->graph, L->spec, d.Fm, 1));
+    s.dwx = w.take((size_t)d.Fo * d.Fo * 4);
+    s.g_sum = w.take((size_t)d.T * d.S * d.fo * 4);
+    s.total = w.total;
     return s;
 }
 }  // namespace
@@ -266,7 +271,7 @@ BwdScratch bwd_scratch(const DgnTowersLayer* L, const Dims& d) {
 extern "C" size_t dgn_towers_layer_backward_workspace_bytes(const DgnTowersLayer* L) {
     Dims d;
     if (!dims_of(L, d, "dgn_towers_layer_backward_workspace_bytes")) return 0;
-    return bwd_scratch(L, d).total;
+    return bwd_ws(L, d).total;
 }
 
 extern "C" int dgn_towers_layer_backward(const DgnTowersLayer* L, const DgnTowersGrads* G, void* stream) {
@@ -278,11 +283,11 @@ extern "C" int dgn_towers_layer_backward(const DgnTowersLayer* L, const DgnTower
     if (!G->g_out || !G->g_h || !G->g_w_sd || !G->g_bias_sd || !G->g_w_post || !G->g_b_post || !G->g_gamma || !G->g_beta || !G->g_w_mix ||
         !G->g_b_mix) { set_error("%s: null gradient buffer", fn); return DGN_ERR_INVALID; }
     if (!drop_ok(L, fn, false)) return DGN_ERR_INVALID;
-    const BwdScratch s = bwd_scratch(L, d);
+    const BwdWs s = bwd_ws(L, d);
     if (!L->ws || L->ws_bytes < s.total) { set_error("%s: workspace too small (%zu < %zu)", fn, L->ws_bytes, s.total); return DGN_ERR_WORKSPACE; }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(L->ws);
-    auto f = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    void* ws = L->ws;
+    auto f = [&](const WsSpan& part) { return part.in<float>(ws); };
     float *g_z = f(s.g_z), *g_y1 = f(s.g_y1), *sums = f(s.sums), *g_yr = f(s.g_yr), *g_aggx = f(s.g_aggx), *g_pq = f(s.g_pq),
           *g_in = f(s.g_in), *g_hpq = f(s.g_hpq);
     // bias + LeakyReLU (+ residual: its gradient is g_out itself, added at the end) and the mixing Linear's input gradient in ONE pass:
@@ -300,7 +305,7 @@ extern "C" int dgn_towers_layer_backward(const DgnTowersLayer* L, const DgnTower
                            (reinterpret_cast<uintptr_t>(L->y0) & 15) == 0 && dgn_linear_bnb_supported(d.Fo, d.Fo) && option(OPT_MIX_BWD_FUSED) != 0;
     if (mix_fused) {
         DGN_TRY(dgn_linear_wgrad_bn_act_mask(d.N, d.Fo, d.Fo, G->g_out, L->zmask, 2, L->slope, L->y0, f(s.dwx), d.Fo, G->g_b_mix, L->save_mean,
-                                             L->save_invstd, nullptr, nullptr, ws + s.wg_mix, dgn_linear_wgrad_workspace_bytes(d.N, d.Fo, d.Fo, 1), stream));
+                                             L->save_invstd, nullptr, nullptr, s.wg_mix.in<char>(ws), s.wg_mix.bytes, stream));
         hipLaunchKernelGGL(mix_bn_finalize, dim3(d.Fo), dim3(64), 0, st, d.Fo, (const float*)f(s.dwx), (const float*)G->g_b_mix, L->w_mix, (int64_t)d.Fo,
                            L->bn_gamma, L->bn_beta, G->g_w_mix, (int64_t)d.Fo, G->g_gamma, G->g_beta, sums);
         DGN_HIP_CHECK(hipGetLastError());
@@ -311,37 +316,34 @@ extern "C" int dgn_towers_layer_backward(const DgnTowersLayer* L, const DgnTower
         else DGN_TRY(dgn_linear_forward_act(d.N, d.Fo, d.Fo, G->g_out, L->z, L->b_mix, 2, L->slope, L->w_mix, d.Fo, 1, g_y1, g_z, stream));
         if (bn_derived) {
             DGN_TRY(dgn_linear_wgrad_bn(d.N, d.Fo, d.Fo, g_z, L->y0, f(s.dwx), d.Fo, G->g_b_mix, L->save_mean, L->save_invstd, nullptr, nullptr,
-                                        ws + s.wg_mix, dgn_linear_wgrad_workspace_bytes(d.N, d.Fo, d.Fo, 1), stream));
+                                        s.wg_mix.in<char>(ws), s.wg_mix.bytes, stream));
             hipLaunchKernelGGL(mix_bn_finalize, dim3(d.Fo), dim3(64), 0, st, d.Fo, (const float*)f(s.dwx), (const float*)G->g_b_mix, L->w_mix, (int64_t)d.Fo,
                                L->bn_gamma, L->bn_beta, G->g_w_mix, (int64_t)d.Fo, G->g_gamma, G->g_beta, sums);
             DGN_HIP_CHECK(hipGetLastError());
         } else {
             DGN_TRY(dgn_linear_wgrad_bn(d.N, d.Fo, d.Fo, g_z, L->y0, G->g_w_mix, d.Fo, G->g_b_mix, L->save_mean, L->save_invstd, L->bn_gamma, L->bn_beta,
-                                        ws + s.wg_mix, dgn_linear_wgrad_workspace_bytes(d.N, d.Fo, d.Fo, 1), stream));
+                                        s.wg_mix.in<char>(ws), s.wg_mix.bytes, stream));
         }
     } else {
         if (!L->z) { set_error("%s: zmask without the fused activation-gradient kernel: give z", fn); return DGN_ERR_INVALID; }
-        DGN_TRY(dgn_bias_act_backward(d.N, d.Fo, G->g_out, L->z, d.Fo, L->b_mix, 2, L->slope, g_z, G->g_b_mix, ws + s.bn_ws,
-                                      dgn_bn_tail_workspace_bytes(d.N, d.Fo), stream));
+        DGN_TRY(dgn_bias_act_backward(d.N, d.Fo, G->g_out, L->z, d.Fo, L->b_mix, 2, L->slope, g_z, G->g_b_mix, s.bn_ws.in<char>(ws), s.bn_ws.bytes, stream));
         // mixing Linear: input and weight gradients
         DGN_TRY(dgn_linear_forward(d.N, d.Fo, d.Fo, 1, g_z, d.Fo, 0, L->w_mix, d.Fo, 0, 1, nullptr, 0, g_y1, d.Fo, 0, stream));
-        if (L->y1) DGN_TRY(dgn_linear_wgrad(d.N, d.Fo, d.Fo, 1, g_z, d.Fo, 0, L->y1, d.Fo, 0, G->g_w_mix, d.Fo, 0, nullptr, 0, ws + s.wg_mix,
-                                            dgn_linear_wgrad_workspace_bytes(d.N, d.Fo, d.Fo, 1), stream));
+        if (L->y1) DGN_TRY(dgn_linear_wgrad(d.N, d.Fo, d.Fo, 1, g_z, d.Fo, 0, L->y1, d.Fo, 0, G->g_w_mix, d.Fo, 0, nullptr, 0, s.wg_mix.in<char>(ws), s.wg_mix.bytes, stream));
         else DGN_TRY(dgn_linear_wgrad_bn(d.N, d.Fo, d.Fo, g_z, L->y0, G->g_w_mix, d.Fo, nullptr, L->save_mean, L->save_invstd, L->bn_gamma, L->bn_beta,
-                                         ws + s.wg_mix, dgn_linear_wgrad_workspace_bytes(d.N, d.Fo, d.Fo, 1), stream));
+                                         s.wg_mix.in<char>(ws), s.wg_mix.bytes, stream));
     }
     // the towers' dropout: the mask on the gradient of the normalised rows, in place         (:275)
     if (L->drop_p > 0.0f) DGN_TRY(dgn_dropout_backward(d.N * d.Fo, g_y1, L->drop_mask, L->drop_p, g_y1, stream));
     // BatchNorm: column sums + affine gradients; its input gradient is formed inside the combine backward
     if (!bn_derived)      // (else: the sums came out of the mixing weight gradient above)
         DGN_TRY(dgn_bn_tail_backward(d.N, d.Fo, g_y1, L->y0, d.Fo, L->bn_gamma, L->bn_beta, L->save_mean, L->save_invstd, 0, nullptr, G->g_gamma,
-                                     G->g_beta, sums, ws + s.bn_ws, dgn_bn_tail_workspace_bytes(d.N, d.Fo), L->n_valid, stream));
+                                     G->g_beta, sums, s.bn_ws.in<char>(ws), s.bn_ws.bytes, L->n_valid, stream));
     if (!mix_fused) {
         DgnBnGrad bn{};
         bn.g_out = g_y1; bn.y = L->y0; bn.ld = d.Fo; bn.gamma = L->bn_gamma; bn.beta = L->bn_beta; bn.mean = L->save_mean; bn.invstd = L->save_invstd;
         bn.sums = sums; bn.relu = 0; bn.n_valid = L->n_valid;
-        DGN_TRY(scale_combine_backward_impl(d.N, d.T, 1, d.fo, nullptr, 0, nullptr, L->snorm, g_yr, G->g_b_post, ws + s.comb_ws,
-                                           dgn_scale_combine_backward_workspace_bytes(d.N, d.T, d.fo), &bn, stream, 1));
+        DGN_TRY(scale_combine_backward_impl(d.N, d.T, 1, d.fo, nullptr, 0, nullptr, L->snorm, g_yr, G->g_b_post, s.comb_ws.in<char>(ws), s.comb_ws.bytes, &bn, stream, 1));
     }
     // posttrans: the scaler expansion happens inside the two products
     DGN_TRY(dgn_linear_combine_backward_input(d.N, d.T, d.S, d.fo, d.K, g_yr, d.N * d.fo, L->scale, L->w_post, d.K, (int64_t)d.S * d.fo * d.K,
@@ -351,7 +353,7 @@ extern "C" int dgn_towers_layer_backward(const DgnTowersLayer* L, const DgnTower
     // (... and the finalize kernel writes that block to g_b_post: no launch of its own)
     DGN_TRY(lin::combine_backward_weight_bias_pick(d.N, d.T, d.S, d.fo, d.K, g_yr, d.N * d.fo, L->scale, L->aggx, d.N * d.K, G->g_w_post, d.K,
                                                    (int64_t)d.S * d.fo * d.K, g_sum, mix_fused ? G->g_b_post : nullptr, mix_fused ? L->id_slot1 - 1 : 0,
-                                                   ws + s.wg_post, dgn_linear_wgrad_workspace_bytes(d.N, d.K, d.S * d.fo, d.T), stream));
+                                                   s.wg_post.in<char>(ws), s.wg_post.bytes, stream));
     // the sweep: d P | d Q in one [N, 2 Fm] buffer, d h_in
     const DgnMsg msg = sweep_msg(L, d);
     DgnMsgGrad gr{};
@@ -359,8 +361,7 @@ extern "C" int dgn_towers_layer_backward(const DgnTowersLayer* L, const DgnTower
     gr.g_dst = g_pq + d.Fm; gr.ld_dst = 2 * d.Fm;
     gr.g_in = g_in; gr.ld_in = d.Fm;
     gr.accumulate = 0;
-    DGN_TRY(dgn_agg_backward_aux(L->graph, L->spec, &msg, L->w, L->ld_w, L->log_deg, g_aggx, d.K, L->agg_aux, &gr, ws + s.agg_ws,
-                                 dgn_agg_backward_workspace_bytes(L->graph, L->spec, d.Fm, 1), stream));
+    DGN_TRY(dgn_agg_backward_aux(L->graph, L->spec, &msg, L->w, L->ld_w, L->log_deg, g_aggx, d.K, L->agg_aux, &gr, s.agg_ws.in<char>(ws), s.agg_ws.bytes, stream));
     // P|Q Linear: input gradient, weight + bias gradient (the bias rides in the weight-gradient pass)
     // d h = [residual] + d h_in + (d P|Q) W_sd: as the product's epilogue ((d h_in + product) + residual, add3's order) where the shapes
     // allow, else the product and a three-way add
@@ -372,19 +373,17 @@ extern "C" int dgn_towers_layer_backward(const DgnTowersLayer* L, const DgnTower
         // the towers' own blocks only: (d h_in + (d P|Q) W_sd) + residual in the product's epilogue, add3's order
         if (option(OPT_BD_BWD_FUSED) && d.fi <= 16 && (reinterpret_cast<uintptr_t>(L->h) & 15) == 0) {
             // ... and its weight gradient in the same pass over d(P|Q) (round 6: bd_backward_both)
-            DGN_TRY(lin::bd_backward_both_launch(d.N, d.T, d.fi, g_pq, L->w_sd, d.Fm, L->h, g_in, res, G->g_h, G->g_w_sd, d.Fm, G->g_bias_sd, ws + s.wg_sd,
-                                                 dgn_linear_bd_wgrad_workspace_bytes(d.N, d.T, d.fi), stream));
+            DGN_TRY(lin::bd_backward_both_launch(d.N, d.T, d.fi, g_pq, L->w_sd, d.Fm, L->h, g_in, res, G->g_h, G->g_w_sd, d.Fm, G->g_bias_sd, s.wg_sd.in<char>(ws),
+                                                 s.wg_sd.bytes, stream));
             return DGN_OK;
         }
         DGN_TRY(dgn_linear_bd_backward_input(d.N, d.T, d.fi, g_pq, L->w_sd, d.Fm, g_in, res, G->g_h, stream));
-        DGN_TRY(dgn_linear_bd_wgrad(d.N, d.T, d.fi, g_pq, L->h, G->g_w_sd, d.Fm, G->g_bias_sd, ws + s.wg_sd,
-                                    dgn_linear_bd_wgrad_workspace_bytes(d.N, d.T, d.fi), stream));
+        DGN_TRY(dgn_linear_bd_wgrad(d.N, d.T, d.fi, g_pq, L->h, G->g_w_sd, d.Fm, G->g_bias_sd, s.wg_sd.in<char>(ws), s.wg_sd.bytes, stream));
         return DGN_OK;
     }
     if (fused_add) DGN_TRY(dgn_linear_forward_add(d.N, 2 * d.Fm, d.Fm, g_pq, L->w_sd, d.Fm, 1, g_in, res, G->g_h, stream));
     else DGN_TRY(dgn_linear_forward(d.N, 2 * d.Fm, d.Fm, 1, g_pq, 2 * d.Fm, 0, L->w_sd, d.Fm, 0, 1, nullptr, 0, g_hpq, d.Fm, 0, stream));
-    DGN_TRY(dgn_linear_wgrad(d.N, d.Fm, 2 * d.Fm, 1, g_pq, 2 * d.Fm, 0, L->h, d.Fm, 0, G->g_w_sd, d.Fm, 0, G->g_bias_sd, 0, ws + s.wg_sd,
-                             dgn_linear_wgrad_workspace_bytes(d.N, d.Fm, 2 * d.Fm, 1), stream));
+    DGN_TRY(dgn_linear_wgrad(d.N, d.Fm, 2 * d.Fm, 1, g_pq, 2 * d.Fm, 0, L->h, d.Fm, 0, G->g_w_sd, d.Fm, 0, G->g_bias_sd, 0, s.wg_sd.in<char>(ws), s.wg_sd.bytes, stream));
     if (fused_add) return DGN_OK;
     const int64_t n = d.N * d.Fm, n4 = n / 4;
     if (al && n4 > 0) {
